@@ -2,7 +2,8 @@
 """Headline benchmark: (start, goal) τ+∇τ evaluations per second, Gibson 3D, 1M pairs per
 GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--total-pairs T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--total-pairs T] [--dump-outputs DIR]
+                    [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` without a torch.distributed environment starts N rank processes itself
@@ -17,6 +18,10 @@ the north star names).  Weak scaling by default (--pairs per rank); --total-pair
 fixed total over the ranks instead (strong scaling).  Rank 0 prints one JSON line; `value` =
 all ranks' pairs / max-over-ranks wall time of the K timed steps.
 
+A plain run sets up, warms up, times the K steps (`ms_per_step` = their wall time / K), writes
+the last step's outputs if `--dump-outputs DIR` is given (dump_outputs) and prints the line.
+
+`--full` adds the secondary legs (`roofline`, `exchange`, `extra`, `cpu_baseline` in the line).
 After the timed steps every rank launches the kernel alone `--roofline-launches` times with
 a HIP event pair around each launch (on the stream it runs on): `roofline.achieved` is the
 algorithmic FLOP of one launch over the mean event-timed duration.  The CPU baseline (rank 0,
@@ -80,6 +85,14 @@ def parse(argv=None):
     ap.add_argument("--force-gather", action="store_true",
                     help="build the RCCL group and run the all-gather even at N = 1 (a "
                          "one-rank collective: measures the exchange path on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs: the per-launch "
+                         "roofline, the exchange split, the extra configs and the CPU baseline "
+                         "(--roofline-launches, --cpu-reps, --no-cpu, --no-extra, --pmc shape "
+                         "them and do nothing without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's tau and dtau, and the "
+                         "gathered rows when the step all-gathers) to DIR/<name>.npy, float32")
     ap.add_argument("--roofline-launches", type=int, default=100)
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true")
@@ -158,6 +171,29 @@ def pmc_traffic(path, pairs, unit_hash):
                       % (os.path.basename(path), j.get("unit_hash"), unit_hash))
     return float(j["hbm_bytes_per_pair"]) * pairs, "PMC %s (unit %s)" % (
         os.path.basename(path), unit_hash)
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000     # all files together stay under 64 MB, headers included
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the last timed step's outputs as float32 `<name>.npy` files: `tau` (n,)
+    and `dtau` (n, 6) of rank 0's batch and, when the step all-gathers, `gathered` (the
+    (n_total, 7) τ|∇τ rows every rank receives).  The inputs are seeded (pntf/synth.py), so
+    two builds run with the same arguments write comparable files.  If all of it exceeds
+    DUMP_BUDGET_BYTES, every array keeps the same share of its rows, picked by a fixed seed
+    (the same rows for arrays of equal length), in ascending order."""
+    names = {"tau": "tau", "dtau": "dtau", "g": "gathered"}
+    arrs = {names[k]: v.detach().to(torch.float32).cpu().numpy()
+            for k, v in res.items() if k in names}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = int(a.shape[0] * (DUMP_BUDGET_BYTES / total))
+            idx = np.random.default_rng(0).choice(a.shape[0], keep, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def timed(step, steps, warmup, ws, sync, dev_for_max):
@@ -258,62 +294,76 @@ def run(args):
         return torch.cat([t.unsqueeze(1), d], 1)
 
     def step():
-        t, d = kernel()
+        t, d = res["tau"], res["dtau"] = kernel()
         if gather:
             res["g"] = dist.all_gather_rows(rows(t, d), n_total, force=args.force_gather)
 
     el = timed(step, args.steps, args.warmup, ws, torch.cuda.synchronize, dev)
     value = n_total * args.steps / el
 
-    # roofline: per-launch HIP events on the launch stream (torch's current stream, which
-    # ops.* hands to the C ABI), kernel alone
-    stream = torch.cuda.current_stream(dev)
-    R = max(args.roofline_launches, args.steps)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(R)]
-    for a, b in evs:
-        a.record(stream)
-        kernel()
-        b.record(stream)
-    torch.cuda.synchronize()
-    kms = np.array([a.elapsed_time(b) for a, b in evs])
-    kern_ms = float(kms.mean())
-    achieved = FLOP_PER_PAIR * n / (kern_ms * 1e-3) / 1e12
-    unit_hash = _lib.build_info().get(HEADLINE_UNIT)
-    traffic, traffic_src = pmc_traffic(args.pmc, n, unit_hash)
-    split = None
-    if gather:
-        # the exchange alone (same row block, same stream), so a scaling run separates
-        # per-rank compute from the xGMI all-gather; every rank's numbers go to rank 0
-        blk = rows(*kernel())
-        dist.all_gather_rows(blk, n_total, force=args.force_gather)
-        torch.cuda.synchronize()
-        gevs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                for _ in range(R)]
-        for a, b in gevs:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    res.clear()
+
+    roofline, split, extra, cpu = None, None, {}, None
+    if args.full:
+        # roofline: per-launch HIP events on the launch stream (torch's current stream, which
+        # ops.* hands to the C ABI), kernel alone
+        stream = torch.cuda.current_stream(dev)
+        R = max(args.roofline_launches, args.steps)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(R)]
+        for a, b in evs:
             a.record(stream)
-            dist.all_gather_rows(blk, n_total, force=args.force_gather)
+            kernel()
             b.record(stream)
         torch.cuda.synchronize()
-        ag_ms = float(np.mean([a.elapsed_time(b) for a, b in gevs]))
-        mine = torch.tensor([kern_ms, ag_ms], dtype=torch.float64, device=dev)
-        every = [torch.zeros_like(mine) for _ in range(tdist.get_world_size())]
-        tdist.all_gather(every, mine)
-        every = torch.stack(every).cpu().numpy()
-        split = {"kernel_ms_per_rank": every[:, 0].tolist(),
-                 "allgather_ms_per_rank": every[:, 1].tolist(),
-                 "allgather_bytes_per_rank": int(blk.numel() * blk.element_size()),
-                 "rccl_world_size": tdist.get_world_size()}
+        kms = np.array([a.elapsed_time(b) for a, b in evs])
+        kern_ms = float(kms.mean())
+        achieved = FLOP_PER_PAIR * n / (kern_ms * 1e-3) / 1e12
+        unit_hash = _lib.build_info().get(HEADLINE_UNIT)
+        traffic, traffic_src = pmc_traffic(args.pmc, n, unit_hash)
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": HEADLINE_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / HEADLINE_PEAK_TFLOPS,
+                    "arithmetic": HEADLINE_ARITHMETIC,
+                    "peak_fp32_mfma": FP32_MFMA_PEAK_TFLOPS,
+                    "achieved_over_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "kernel": "wide_field_kernel<3,K_TAU_GRAD>", "unit_hash": unit_hash,
+                    "kernel_ms": kern_ms, "kernel_ms_min": float(kms.min()),
+                    "kernel_ms_max": float(kms.max()), "launches_timed": R,
+                    "flop_per_pair": FLOP_PER_PAIR,
+                    "algorithmic_bytes_per_pair": BYTES_PER_PAIR}
+        if gather:
+            # the exchange alone (same row block, same stream), so a scaling run separates
+            # per-rank compute from the xGMI all-gather; every rank's numbers go to rank 0
+            blk = rows(*kernel())
+            dist.all_gather_rows(blk, n_total, force=args.force_gather)
+            torch.cuda.synchronize()
+            gevs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    for _ in range(R)]
+            for a, b in gevs:
+                a.record(stream)
+                dist.all_gather_rows(blk, n_total, force=args.force_gather)
+                b.record(stream)
+            torch.cuda.synchronize()
+            ag_ms = float(np.mean([a.elapsed_time(b) for a, b in gevs]))
+            mine = torch.tensor([kern_ms, ag_ms], dtype=torch.float64, device=dev)
+            every = [torch.zeros_like(mine) for _ in range(tdist.get_world_size())]
+            tdist.all_gather(every, mine)
+            every = torch.stack(every).cpu().numpy()
+            split = {"kernel_ms_per_rank": every[:, 0].tolist(),
+                     "allgather_ms_per_rank": every[:, 1].tolist(),
+                     "allgather_bytes_per_rank": int(blk.numel() * blk.element_size()),
+                     "rccl_world_size": tdist.get_world_size()}
 
-    extra = {}
-    if not args.no_extra:
-        if ws == 1:
-            extra = extras(packed, dev)
-        else:
-            extra = sharded_extras(packed, dev, rank, ws)
-    cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu:
-        cpu = cpu_baseline(reps=args.cpu_reps)        # last: after every GPU leg
+        if not args.no_extra:
+            if ws == 1:
+                extra = extras(packed, dev)
+            else:
+                extra = sharded_extras(packed, dev, rank, ws)
+        if rank == 0 and ws == 1 and not args.no_cpu:
+            cpu = cpu_baseline(reps=args.cpu_reps)        # last: after every GPU leg
 
     if rank == 0:
         line = {
@@ -328,19 +378,10 @@ def run(args):
                        "parallelism": "dp%d" % ws,
                        "rccl_world_size": tdist.get_world_size() if tdist.is_initialized()
                        else 1},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": HEADLINE_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / HEADLINE_PEAK_TFLOPS,
-                         "arithmetic": HEADLINE_ARITHMETIC,
-                         "peak_fp32_mfma": FP32_MFMA_PEAK_TFLOPS,
-                         "achieved_over_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "wide_field_kernel<3,K_TAU_GRAD>", "unit_hash": unit_hash,
-                         "kernel_ms": kern_ms, "kernel_ms_min": float(kms.min()),
-                         "kernel_ms_max": float(kms.max()), "launches_timed": R,
-                         "flop_per_pair": FLOP_PER_PAIR,
-                         "algorithmic_bytes_per_pair": BYTES_PER_PAIR},
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line["roofline"] = roofline
+            line["cpu_baseline"] = cpu
         if split:
             line["exchange"] = split
         if extra:

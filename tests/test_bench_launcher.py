@@ -62,6 +62,43 @@ def test_world_size_mismatch_fails():
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_arrays_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: whole arrays while they fit; above the budget the same seeded, ordered
+    share of every array's rows (equal rows for arrays of equal length), run after run."""
+    import numpy as np
+    import torch
+    import bench
+    n = 1000
+    res = {"tau": torch.arange(n, dtype=torch.float32),
+           "dtau": torch.arange(n, dtype=torch.float32).unsqueeze(1).repeat(1, 6)}
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    tau, dtau = np.load(tmp_path / "a" / "tau.npy"), np.load(tmp_path / "a" / "dtau.npy")
+    assert tau.dtype == np.float32 and dtau.dtype == np.float32
+    assert np.array_equal(tau, res["tau"].numpy()) and np.array_equal(dtau, res["dtau"].numpy())
+    assert sorted(os.listdir(tmp_path / "a")) == ["dtau.npy", "tau.npy"]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 7 * 4 * n // 4)
+    res["g"] = torch.arange(2 * n, dtype=torch.float64).unsqueeze(1).repeat(1, 7)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    got = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in ("tau", "dtau", "gathered")}
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET_BYTES
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert len(got["tau"]) == len(got["dtau"]) > 0 and len(got["gathered"]) > 0
+    assert np.array_equal(got["tau"], got["dtau"][:, 0]) and np.all(np.diff(got["tau"]) > 0)
+    assert np.all(np.diff(got["gathered"][:, 0]) > 0)
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "c" / (k + ".npy")))
+
+
 def test_failed_rank_fails_the_job():
     """A rank that dies makes the launcher exit non-zero instead of hanging the others."""
     sys.path.insert(0, os.path.join(ROOT, "p-ntfields_amd"))

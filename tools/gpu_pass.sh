@@ -7,7 +7,7 @@
 # steps (each under its own time limit, chained: the first failure ends the pass):
 #   tests[=<pytest args>]  the -m gpu suite (default: all of tests/), log <tag>_gpu_tests.log;
 #                          alltests[=...] runs past failures (reports them, goes on)
-#   bench                  the default bench.py line -> <tag>_bench.json
+#   bench                  the complete `bench.py --full` line -> <tag>_bench.json
 #   head                   headline kernel: rocprofv3 stats over 20 steps + FETCH/WRITE/MFMA/
 #                          stall PMC passes (tools/profile_round.sh) -> <tag>_prof/
 #   c5                     C5 planner: kernel trace + stats, then the SQ / TCC / LDS PMC passes
@@ -44,7 +44,7 @@ for step in "$@"; do
         [ -n "$x" ] || [ $rc -ne 1 ] && exit 1
       fi ;;
     bench)
-      timeout -k 10 900 python3 bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" \
+      timeout -k 10 900 python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" \
         || { tail -30 "$OUT/${TAG}_bench.err"; exit 1; }
       cat "$OUT/${TAG}_bench.json" ;;
     head)

@@ -119,15 +119,12 @@ constexpr int OFF_QUAD = (OFF_WIDE + W_SZ + 63) / 64 * 64;
 constexpr int Q_OFF_AUX = Q_WAVES * Q_STREAM;
 constexpr int Q_SZ = Q_OFF_AUX + Q_WAVES * Q_NAUX * 256;
 constexpr int PACKED_TOTAL = OFF_QUAD + Q_SZ;
-// Split-bf16 wide fragments (pntf_wide.h, PNTF_WIDE_X6): the wide region's two directions
-// regrouped per 32 x 32 step into 2 k blocks x 3 bf16 terms (1.5x the fp32 bytes; a matrix at
-// fp32 wide offset o sits at 1.5 o here)
+// Split-bf16 wide fragments (pntf_wide.h): the wide region's two directions regrouped per
+// 32 x 32 step into 2 k blocks x 3 bf16 terms, in each layer's step order (1.5x the fp32 bytes;
+// a matrix at fp32 wide offset o sits at 1.5 o here)
 constexpr int OFF_X6 = (PACKED_TOTAL + 63) / 64 * 64;
 constexpr int X6_SZ = 3 * SZ_DIR;
-// the same in block-major step order for the two-column (encoder) layers (pntf_wide.h
-// wx6_block_major; other layers' order is unchanged)
-constexpr int OFF_X6BM = OFF_X6 + X6_SZ;
-constexpr int PACKED_TOTAL_X6 = OFF_X6BM + X6_SZ;
+constexpr int PACKED_TOTAL_X6 = OFF_X6 + X6_SZ;
 // Split-bf16 narrow fragments (pntf_taylor.h, the residual kernel's Taylor directions on
 // v_mfma_f32_16x16x32_bf16, round 6): the forward direction regrouped per (16-row out tile,
 // 32-feature k block) into 3 bf16 terms of 1 KiB each, in taylor_layer_x6's step order (out

@@ -127,16 +127,12 @@ UNITS = (
     + [("fsplit_d%d_k%d" % (d, k), "pntf_kernels.hip",
         ["-DPNTF_DIM=%d" % d, "-DPNTF_KIND=%d" % k, "-DPNTF_SPLIT_FIELD"])
        for d in (3, 6) for k in range(5)]
-    # wide kernels (pntf_wide.h): a 2-step ring (32-64 fp32 MFMAs of 64 cycles ahead; 24-48
-    # bf16 MFMAs of 32 cycles in the split-bf16 layers, 6 fragments per step)
-    # (block-major encoder layers, PNTF_X6_BM, where they stay spill-free: τ, travel time, and
-    # τ+∇τ at dim 3 — the headline)
-    # (round 6: the accumulate-in-bank engine, pntf_wide.h xlayer; the dim-6 units, whose
-    # 12-float pair state sits beside the ring, run a 1-step ring to stay spill-free)
+    # wide kernels (pntf_wide.h): split-bf16 layers read 6 fragments per step (PNTF_RING_NL);
+    # a 2-step ring at dim 3 (24-48 bf16 MFMAs of 32 cycles ahead); the dim-6 units, whose
+    # 12-float pair state sits beside the ring, run a 1-step ring to stay spill-free
     + [("wide_d%d_k%d" % (d, k), "pntf_kernels.hip",
         ["-DPNTF_DIM=%d" % d, "-DPNTF_KIND=%d" % k, "-DPNTF_WIDE_FIELD",
-         "-DPNTF_PF_STEPS=%d" % (2 if d == 3 else 1),
-         "-DPNTF_WIDE_X6=1", "-DPNTF_RING_NL=6", "-DPNTF_X6_BM=%d" % (k in (0, 4) or (d, k) == (3, 1))])
+         "-DPNTF_PF_STEPS=%d" % (2 if d == 3 else 1), "-DPNTF_RING_NL=6"])
        for d in (3, 6) for k in range(5)]
     # plan_kernel<6> holds the 6-dof path state beside the ring: a 2-step ring keeps it
     # spill-free (the 4-step ring spills 2 VGPRs there).
@@ -251,10 +247,13 @@ def _compile(unit, uid=None):
         raise RuntimeError("VGPR spills / scratch in %s: %s" % (name, bad))
     if SGPR_SPILL_FREE.match(name):
         # the env-table-in-LDS instantiation (BL = true, "Lb1E": the headline's, <= 13 envs at
-        # dim 3); the global-table one of the accumulate-in-bank engine keeps a few SGPR
-        # spills to VGPR lanes beside its B pointers (round 6)
-        sbad = {k: v["SGPRs Spill"] for k, v in res.items()
-                if v.get("SGPRs Spill", 0) and "Lb1E" in k}
+        # dim 3); the global-table one keeps a few SGPR spills to VGPR lanes beside its B
+        # pointers.  No "Lb1E" kernel in the report would pass the gate vacuously: fail then.
+        lds = {k: v for k, v in res.items() if "Lb1E" in k}
+        if not lds:
+            raise RuntimeError("no env-table-in-LDS (Lb1E) kernel reported for %s: %s"
+                               % (name, sorted(res)))
+        sbad = {k: v["SGPRs Spill"] for k, v in lds.items() if v.get("SGPRs Spill", 0)}
         if sbad:
             raise RuntimeError("SGPR spills in %s (must stay spill-free): %s" % (name, sbad))
     for asm in glob.glob(os.path.join(d, "*amdgcn*gfx950*.s")):

@@ -46,18 +46,14 @@ extern "C" int perf_tau_grad(int grid, const float* P, const float* xp, int64_t 
 }
 
 #ifdef PERF_WIDE
-// floats of the blob this build reads, and the split-bf16 region of an x6 build: P holds that
-// many floats, the first PACKED_TOTAL of them the production blob
-extern "C" long long perf_packed_total() {
-  return PNTF_WIDE_X6 ? pntf::PACKED_TOTAL_X6 : pntf::PACKED_TOTAL;
-}
+// floats of the blob this build reads (through the split-bf16 region OFF_X6): P holds that
+// many floats, the first PACKED_TOTAL of them the fp32 layouts
+extern "C" long long perf_packed_total() { return pntf::PACKED_TOTAL_X6; }
 extern "C" int perf_pack_x6(float* P, hipStream_t stream) {
   using namespace pntf;
   const int64_t n = (int64_t)(2 * SZ_DIR / 1024) * 2 * 64;
-  for (int bm = 0; bm < 2; ++bm)
-    hipLaunchKernelGGL(pack_x6_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                       P + OFF_WIDE, reinterpret_cast<uint16_t*>(P + (bm ? OFF_X6BM : OFF_X6)),
-                       bm);
+  hipLaunchKernelGGL(pack_x6_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     P + OFF_WIDE, reinterpret_cast<uint16_t*>(P + OFF_X6));
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 #endif

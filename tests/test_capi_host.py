@@ -53,12 +53,12 @@ def test_pure_queries_without_gpu(lib):
     # then (64-float aligned) the quad streams: both directions once more, and per wave (8 per
     # quad workgroup) 14 bias / head fragments
     off_quad = (2 * mats + plain + wide + 63) // 64 * 64
-    # then (64-float aligned) two split-bf16 copies of the wide matrices (3 bf16 terms per
-    # weight; the second in block-major order for the encoder layers)
+    # then (64-float aligned) the split-bf16 copy of the wide matrices (3 bf16 terms per weight:
+    # 1.5 floats, both directions)
     off_x6 = (off_quad + 2 * mats + 8 * 14 * 256 + 63) // 64 * 64
     # then the forward matrices split for the residual kernel's 16x16x32 Taylor layers
-    off_nx6 = (off_x6 + 2 * 3 * mats + 63) // 64 * 64
-    assert lib.pntf_packed_floats() == off_nx6 + 3 * mats // 2
+    off_nx6 = (off_x6 + 3 * mats + 63) // 64 * 64
+    assert lib.pntf_packed_floats() == off_nx6 + 3 * mats // 2 == 5717312
     lib.pntf_status_string.restype = ctypes.c_char_p
     assert lib.pntf_status_string(1) == b"invalid argument"
 
@@ -345,11 +345,12 @@ def test_store_data_guard_catches_an_unguarded_build(tmp_path):
     import subprocess
     from pntf import build
     out = str(tmp_path / "variant.s")
+    defs, = [d for name, _, d in build.UNITS if name == "wide_d3_k1"]   # the shipped kernel's
     cmd = ([build.hipcc()] + [f for f in build.CXXFLAGS if not f.startswith(("-save-temps",
                                                                             "-Rpass"))]
-           + ["-DPNTF_DIM=3", "-DPNTF_KIND=1", "-DPNTF_WIDE_FIELD", "-DPNTF_PF_STEPS=2", "-DPNTF_BSTORE_UNGUARDED",
-              "--cuda-device-only", "-S", os.path.join(build.CSRC, "pntf_kernels.hip"),
-              "-o", out])
+           + defs + ["-DPNTF_BSTORE_UNGUARDED",
+                     "--cuda-device-only", "-S", os.path.join(build.CSRC, "pntf_kernels.hip"),
+                     "-o", out])
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0 and "not found" in r.stderr:
         pytest.skip("hipcc unavailable")

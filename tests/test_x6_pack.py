@@ -1,15 +1,13 @@
-"""The split-bf16 copies of the wide weight fragments (pntf_wide.h pack_x6_kernel, DESIGN.md §3
-"split-bf16 layers"), read back from the packed blob and checked against their definition:
+"""The split-bf16 copy of the wide weight fragments (pntf_wide.h pack_x6_kernel, DESIGN.md §3
+"split-bf16 layers"), read back from the packed blob and checked against its definition:
 
-  * every weight of the fp32 wide region (both directions, every matrix) appears once in each
-    copy, at the fragment the wide kernel's step order reads it from: per 32 x 32 step (ot, kt)
-    and k block b, element i of lane l holds M[32 ot + (l & 31)][32 kt + (i & 3) + 16 b +
-    8 (i >> 2) + 4 (l >> 5)], i.e. element i & 3 of fp32 fragment 2b + (i >> 2);
-  * step order of the first copy (OFF_X6): every layer's out tiles in one group, steps
-    (kt, ot), fragments 3b + term, for the accumulate-in-bank engine (round 6; encoder[0]^T, the
-    Fourier fold, in two passes (p, kt, ot_local) of its sin/cos tiles 2p, 2p + 1); round 5's
-    groups of 4 / per tile with X6_ACC = False; the second copy (OFF_X6BM) block-major
-    (g of 2 tiles, kt, b), fragments 3o + term, for the two-column layers;
+  * every weight of the fp32 wide region (both directions, every matrix) appears once in the
+    copy (OFF_X6), at the fragment the wide kernel's step order reads it from: per 32 x 32 step
+    (ot, kt) and k block b, element i of lane l holds M[32 ot + (l & 31)][32 kt + (i & 3) +
+    16 b + 8 (i >> 2) + 4 (l >> 5)], i.e. element i & 3 of fp32 fragment 2b + (i >> 2);
+  * step order: every layer's out tiles in one group, steps (kt, ot), fragments 3b + term
+    (pntf_wide.h xlayer); encoder[0]^T, the Fourier fold, in two passes (p, kt, ot_local) of its
+    sin/cos tiles 2p, 2p + 1;
   * the three terms are the round-to-nearest-even bf16 splits x0 = bf16(x), x1 = bf16(x - x0),
     x2 = bf16(x - x0 - x1), bit for bit, and x0 + x1 + x2 == x exactly.
 """
@@ -42,26 +40,16 @@ def bf16_rne(x):
     return (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
 
 
-# The step order of the first copy follows the wide kernel's layer engine (pntf_wide.h):
-# PNTF_X6_ACC = 1 (round 6, the accumulate-in-bank xlayer): every layer's out tiles in one group,
-# steps (kt, ot); encoder[0]^T (the Fourier fold) in two passes of 4 out tiles.  Round 5's
-# engine: groups of 4 (one-column) / per tile (two-column layers).
-X6_ACC = True
-
-
-def frag_index(gf, j, OT, KT, nc, b, bm, fold=False):
+# The step order follows the wide kernel's layer engine (pntf_wide.h xlayer): every layer's out
+# tiles in one group, steps (kt, ot); encoder[0]^T (the Fourier fold) in two passes of 4 out
+# tiles.
+def frag_index(gf, j, OT, KT, b, fold=False):
     ot, kt = divmod(j, KT)
     base = gf - j
-    if nc == 2 and bm:
-        return (base + ((ot // 2) * KT + kt) * 2 + b) * 6 + (ot % 2) * 3
-    if X6_ACC and fold:
+    if fold:
         p, ol = (ot % 4) // 2, ((ot % 4) % 2) * 2 + ot // 4
         return (base + (p * KT + kt) * 4 + ol) * 6 + 3 * b
-    if X6_ACC:
-        G = min(OT, 8) if nc == 1 else 4
-    else:
-        G = 1 if nc == 2 else 4
-    return (base + (ot // G) * KT * G + kt * G + ot % G) * 6 + 3 * b
+    return (base + kt * OT + ot) * 6 + 3 * b
 
 
 def test_x6_copies_match_their_definition():
@@ -69,8 +57,7 @@ def test_x6_copies_match_their_definition():
     packed = ops.pack_weights([torch.from_numpy(v).to(dev) for v in weights().values()])
     P = packed.cpu().numpy()
     x6_sz = 3 * SZ_DIR
-    off_bm = P.size - NX6_SZ - x6_sz      # the narrow split copy (round 6) comes last
-    off_x6 = off_bm - x6_sz
+    off_x6 = P.size - NX6_SZ - x6_sz      # the narrow split copy comes last
     off_wide = 2 * SZ_DIR + SZ_BIAS
     wide = P[off_wide:off_wide + 2 * SZ_DIR].reshape(-1, 4, 64, 4)     # step, u, lane, s
     # fp32 values of (step, block, lane, i): element i & 3 of fragment 2b + (i >> 2)
@@ -80,23 +67,22 @@ def test_x6_copies_match_their_definition():
     x2 = bf16_rne(vals - x0 - x1)
     assert np.array_equal(x0.astype(np.float64) + x1 + x2, vals.astype(np.float64))
     want = np.stack([x0, x1, x2], axis=2)                              # step, b, term, lane, i
-    for off, bm in ((off_x6, False), (off_bm, True)):
-        bits = P[off:off + x6_sz].view(np.uint16).reshape(-1, 64, 8).astype(np.uint32) << 16
-        got = bits.view(np.float32)                                   # fragment, lane, i
-        seen = np.zeros(got.shape[0], dtype=np.int32)
-        for d in (0, 1):
-            for m0, out, inn, nc in MATS:
-                if d:
-                    out, inn = inn, out
-                OT, KT = out // 32, inn // 32
-                for j in range(OT * KT):
-                    gf = (d * SZ_DIR + m0) // 1024 + j
-                    for b in range(2):
-                        fr = frag_index(gf, j, OT, KT, nc, b, bm, fold=(d == 1 and m0 == 0))
-                        for p in range(3):
-                            assert np.array_equal(got[fr + p], want[gf, b, p]), (d, m0, j, b, p, bm)
-                            seen[fr + p] += 1
-        assert (seen == 1).all(), "every fragment written once"
+    bits = P[off_x6:off_x6 + x6_sz].view(np.uint16).reshape(-1, 64, 8).astype(np.uint32) << 16
+    got = bits.view(np.float32)                                       # fragment, lane, i
+    seen = np.zeros(got.shape[0], dtype=np.int32)
+    for d in (0, 1):
+        for m0, out, inn, _ in MATS:
+            if d:
+                out, inn = inn, out
+            OT, KT = out // 32, inn // 32
+            for j in range(OT * KT):
+                gf = (d * SZ_DIR + m0) // 1024 + j
+                for b in range(2):
+                    fr = frag_index(gf, j, OT, KT, b, fold=(d == 1 and m0 == 0))
+                    for p in range(3):
+                        assert np.array_equal(got[fr + p], want[gf, b, p]), (d, m0, j, b, p)
+                        seen[fr + p] += 1
+    assert (seen == 1).all(), "every fragment written once"
 
 
 def test_nx6_copy_matches_its_definition():

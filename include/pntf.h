@@ -386,6 +386,39 @@ int pntf_point_mesh_distance(const float* pts, int64_t n, const float* tris, int
 int pntf_mesh_chunks(int64_t n, int64_t t);
 const char* pntf_mesh_last_error(void);
 
+/* Arm -> mesh distance (pntf_arm.hip): for each of n joint vectors `theta` (n, dof) the
+ * minimum distance from every collision vertex of the posed serial chain to the mesh,
+ *   dist[c] = min(cap, min over frames f, vertices v of f, triangles T of
+ *                      dist(M_f(theta[c]) · v, T)),
+ * what arm_obstacle_distance returns (dataprocessing/speed_sampling_gpu.py:153-218:
+ * pytorch_kinematics forward_kinematics(th, end_only=False), the posed n x V cloud,
+ * bvh_distance_queries, sqrt, torch.min per configuration), without the cloud in memory.
+ *
+ * The chain has `frames` frames (1..PNTF_ARM_MAX_FRAMES), root first, posed by the URDF
+ * convention M_f = M_{f-1} · O_f · J_f(theta): `origins` (frames, 3, 4) fixed transforms O_f
+ * (row-major, last row 0 0 0 1 implied), `types` (frames) PNTF_JOINT_*, `axes` (frames, 3)
+ * UNIT joint axes, `cols` (frames) the column of theta a revolute / prismatic joint reads
+ * (< dof <= PNTF_ARM_MAX_DOF; ignored for fixed joints).  J_f is the rotation by theta about
+ * the axis, the translation by theta along it, or the identity.  `voff` (frames + 1) are CSR
+ * offsets into `verts` (V, 3), the link-local vertices of each frame (a frame may own none).
+ * The four chain tables and `voff` are HOST pointers (an exception to the convention above):
+ * they are small, validated before any device access and travel to the kernel as arguments.
+ * `theta`, `verts`, `tris` (t, 3, 3) and `dist` (n) are device pointers.
+ * `cap` >= 0 bounds the result (INFINITY = exact) and serves the kernel as a culling bound;
+ * the result equals min(cap, exact result) bit for bit, and its bits depend neither on how
+ * the vertices are chunked nor on the other rows of the batch.  full-precision sinf / cosf.
+ * Errors are reported by pntf_mesh_last_error. */
+#define PNTF_ARM_MAX_FRAMES 16
+#define PNTF_ARM_MAX_DOF 16
+#define PNTF_JOINT_FIXED 0
+#define PNTF_JOINT_REVOLUTE 1
+#define PNTF_JOINT_PRISMATIC 2
+int pntf_arm_mesh_distance(const float* theta, int64_t n, int dof, int frames,
+                           const float* origins, const int32_t* types, const float* axes,
+                           const int32_t* cols, const float* verts, const int32_t* voff,
+                           const float* tris, int64_t t, float cap, float* dist,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

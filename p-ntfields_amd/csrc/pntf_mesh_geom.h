@@ -1,0 +1,120 @@
+// Point -> triangle geometry shared by the mesh-distance kernels (pntf_mesh.hip: points given;
+// pntf_arm.hip: points posed by forward kinematics in the kernel): the per-triangle LDS record,
+// the branch-free squared distance and the wave reductions.  One definition, so both kernels
+// compute a (point, triangle) pair to the same bits.
+#ifndef PNTF_MESH_GEOM_H_
+#define PNTF_MESH_GEOM_H_
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+namespace pntf_mesh {
+
+// thread-local error text behind pntf_mesh_last_error (defined in pntf_mesh.hip)
+char* error_buffer();
+constexpr int ERROR_BYTES = 512;
+
+constexpr int BLOCK = 256;       // lanes per workgroup = triangles per LDS tile
+constexpr int PTS = 4;           // points per lane, in registers
+constexpr int PPW = BLOCK * PTS; // points per workgroup
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by,
+                                      float bz) {
+  return fmaf(ax, bx, fmaf(ay, by, az * bz));
+}
+
+// Per-triangle record staged in LDS (8 float4, built once per tile by one lane each):
+//   [0] a, 1/|ab|^2   [1] ab, 1/|ac|^2   [2] ac, 1/|bc|^2   [3] bc, flat
+//   [4] n^ (unit normal)   [5] m_ab = n^ x ab   [6] m_ac = ac x n^   [7] m_bc = n^ x bc
+// m_* are in-plane edge normals pointing into the triangle; `flat` = 1 for a (near-)zero-area
+// triangle (sin^2 of the angle at a <= 1e-12), whose distance is then its nearest edge.
+//   [8] triangle AABB min   [9] triangle AABB max   (tile culling, see the kernels)
+constexpr int REC = 10;
+
+__device__ __forceinline__ void build_record(const float* __restrict__ t, float4* __restrict__ r) {
+  const float ax = t[0], ay = t[1], az = t[2];
+  const float abx = t[3] - ax, aby = t[4] - ay, abz = t[5] - az;
+  const float acx = t[6] - ax, acy = t[7] - ay, acz = t[8] - az;
+  const float bcx = t[6] - t[3], bcy = t[7] - t[4], bcz = t[8] - t[5];
+  const float ab2 = dot3(abx, aby, abz, abx, aby, abz);
+  const float ac2 = dot3(acx, acy, acz, acx, acy, acz);
+  const float bc2 = dot3(bcx, bcy, bcz, bcx, bcy, bcz);
+  float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+  const float nn = dot3(nx, ny, nz, nx, ny, nz);
+  const bool flat = !(nn > 1e-12f * ab2 * ac2);
+  const float inv = flat ? 0.f : 1.f / sqrtf(nn);
+  nx *= inv; ny *= inv; nz *= inv;
+  r[0] = make_float4(ax, ay, az, ab2 > 0.f ? 1.f / ab2 : 0.f);
+  r[1] = make_float4(abx, aby, abz, ac2 > 0.f ? 1.f / ac2 : 0.f);
+  r[2] = make_float4(acx, acy, acz, bc2 > 0.f ? 1.f / bc2 : 0.f);
+  r[3] = make_float4(bcx, bcy, bcz, flat ? 1.f : 0.f);
+  r[4] = make_float4(nx, ny, nz, 0.f);
+  r[5] = make_float4(ny * abz - nz * aby, nz * abx - nx * abz, nx * aby - ny * abx, 0.f);
+  r[6] = make_float4(acy * nz - acz * ny, acz * nx - acx * nz, acx * ny - acy * nx, 0.f);
+  r[7] = make_float4(ny * bcz - nz * bcy, nz * bcx - nx * bcz, nx * bcy - ny * bcx, 0.f);
+  r[8] = make_float4(fminf(ax, fminf(t[3], t[6])), fminf(ay, fminf(t[4], t[7])),
+                     fminf(az, fminf(t[5], t[8])), 0.f);
+  r[9] = make_float4(fmaxf(ax, fmaxf(t[3], t[6])), fmaxf(ay, fmaxf(t[4], t[7])),
+                     fmaxf(az, fmaxf(t[5], t[8])), 0.f);
+}
+
+// workgroup-wide min / max of 256 lanes (4 waves): wave shuffles, then LDS
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// squared distance from q (= p - origin) to the segment origin + [0,1]·e, 1/|e|^2 = ie
+__device__ __forceinline__ float seg_d2(float qx, float qy, float qz, float4 e, float ie) {
+  const float tt = fminf(fmaxf(dot3(qx, qy, qz, e.x, e.y, e.z) * ie, 0.f), 1.f);
+  const float rx = fmaf(-tt, e.x, qx), ry = fmaf(-tt, e.y, qy), rz = fmaf(-tt, e.z, qz);
+  return dot3(rx, ry, rz, rx, ry, rz);
+}
+
+// Branch-free |p - closest point of the triangle|^2: if p projects inside the triangle the
+// distance is the plane distance, otherwise the nearest of the three edges (exactly the
+// Voronoi regions of Ericson §5.1.5, evaluated without divergence: every lane of a wave
+// runs the same instructions whatever region its point falls in).
+__device__ __forceinline__ float tri_d2(float px, float py, float pz,
+                                        const float4* __restrict__ r) {
+  const float4 a = r[0], ab = r[1], ac = r[2], bc = r[3];
+  const float qx = px - a.x, qy = py - a.y, qz = pz - a.z;           // p - a
+  const float bx = qx - ab.x, by = qy - ab.y, bz = qz - ab.z;        // p - b
+  float e = fminf(seg_d2(qx, qy, qz, ab, a.w), seg_d2(qx, qy, qz, ac, ab.w));
+  e = fminf(e, seg_d2(bx, by, bz, bc, ac.w));
+  const float4 n = r[4], m0 = r[5], m1 = r[6], m2 = r[7];
+  const float h = dot3(qx, qy, qz, n.x, n.y, n.z);
+  const bool inside = dot3(qx, qy, qz, m0.x, m0.y, m0.z) >= 0.f &&
+                      dot3(qx, qy, qz, m1.x, m1.y, m1.z) >= 0.f &&
+                      dot3(bx, by, bz, m2.x, m2.y, m2.z) >= 0.f && bc.w == 0.f;
+  return inside ? fminf(h * h, e) : e;
+}
+
+// Exact tile culling, shared so both kernels skip by the same rule: a triangle whose AABB
+// [bmin, bmax] is farther from the point box [lo, hi] than `bound` (a squared distance no
+// point of the box needs to beat) cannot lower a minimum.  Cull only with slack: gap^2 and
+// tri_d2 are both fp32-rounded, and a triangle whose true distance sits within a few ulp of
+// the box gap (axis-aligned walls) could otherwise be culled although its computed d2 is
+// below the bound.  The slack covers both roundings: relative to the bound, and absolute on
+// the squared coordinate scale of the triangle and the point box (pext = its largest
+// |coordinate|).
+__device__ __forceinline__ bool tri_culled(float4 bmin, float4 bmax, const float* lo,
+                                           const float* hi, float pext, float bound) {
+  const float gx = fmaxf(fmaxf(bmin.x - hi[0], lo[0] - bmax.x), 0.f);
+  const float gy = fmaxf(fmaxf(bmin.y - hi[1], lo[1] - bmax.y), 0.f);
+  const float gz = fmaxf(fmaxf(bmin.z - hi[2], lo[2] - bmax.z), 0.f);
+  const float ext = fmaxf(fmaxf(fmaxf(fabsf(bmin.x), fabsf(bmax.x)),
+                                fmaxf(fmaxf(fabsf(bmin.y), fabsf(bmax.y)),
+                                      fmaxf(fabsf(bmin.z), fabsf(bmax.z)))), pext);
+  return dot3(gx, gy, gz, gx, gy, gz) > bound * (1.f + 1e-4f) + 1e-6f * ext * ext;
+}
+
+}  // namespace pntf_mesh
+
+#endif  // PNTF_MESH_GEOM_H_

@@ -2,6 +2,7 @@
 
 Host runtime for libpntf.so (HIP, gfx950).  `pntf.ops` holds the torch-facing entry
 points, `pntf.net` the pieces shared by the drop-in `models` modules, `pntf.synth` the
-seeded synthetic inputs, `pntf.dist` the multi-GPU sharding.
+seeded synthetic inputs, `pntf.dist` the multi-GPU sharding, `pntf.kin` the serial chains
+(URDF) of the arm sampler.
 """
 __version__ = "0.1.0"

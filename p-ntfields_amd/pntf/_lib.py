@@ -130,6 +130,12 @@ SIGNATURES = {
                                                 ctypes.c_int, _c_void_p]),
     "pntf_mesh_chunks": (ctypes.c_int, [_i64, _i64]),
     "pntf_mesh_last_error": (ctypes.c_char_p, []),
+    # arm sampler (pntf_arm.hip): theta, n, dof, frames, origins, types, axes, cols (host
+    # tables), verts, voff (host), tris, t, cap, dist, stream
+    "pntf_arm_mesh_distance": (ctypes.c_int, [_c_void_p, _i64, ctypes.c_int, ctypes.c_int,
+                                              _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                              _c_void_p, _c_void_p, _c_void_p, _i64, _f32,
+                                              _c_void_p, _c_void_p]),
 }
 
 _lib = None
@@ -170,7 +176,7 @@ def check(status, what):
         lib = load()
         if what.startswith(("pntf_tt_", "pntf_adamw")):
             err = lib.pntf_tt_last_error()
-        elif what.startswith("pntf_point_mesh"):
+        elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh")):
             err = lib.pntf_mesh_last_error()
         else:
             err = lib.pntf_last_error()

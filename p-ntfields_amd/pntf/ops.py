@@ -12,6 +12,7 @@ mutates process-wide library state.
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -19,7 +20,8 @@ from ._lib import GRAD_BACKGRAD_COMPAT, GRAD_EXACT, PntfError, check
 
 __all__ = ["GRAD_EXACT", "GRAD_BACKGRAD_COMPAT", "PntfError", "pack_weights", "tau",
            "tau_grad", "path_velocity", "speed", "travel_time", "plan", "eikonal_residual",
-           "device_sum", "packed_floats", "workspace_bytes", "point_mesh_distance"]
+           "device_sum", "packed_floats", "workspace_bytes", "point_mesh_distance",
+           "arm_mesh_distance"]
 
 class StreamScratch:
     """Grow-only device scratch per (device, stream), least-recently-used first out.
@@ -320,4 +322,65 @@ def point_mesh_distance(pts, tris, chunks=0, order=None):
           "pntf_point_mesh_distance")
     if order:
         out[perm] = res
+    return out
+
+
+def _link_vertices(chain, link_verts, device):
+    """verts (V, 3) on the device and the frames' CSR offsets (F + 1,) int32 on the host."""
+    F = len(chain.link_names)
+    if isinstance(link_verts, dict):
+        unknown = sorted(set(link_verts) - set(chain.link_names))
+        if unknown:
+            raise PntfError("link_verts names links that are not in the chain: %s" % unknown)
+        link_verts = [link_verts.get(name) for name in chain.link_names]
+    link_verts = list(link_verts)
+    if len(link_verts) != F:
+        raise PntfError("link_verts must be a dict by link name or a list of %d entries (one "
+                        "per frame), got %d" % (F, len(link_verts)))
+    parts, voff = [], np.zeros(F + 1, dtype=np.int64)
+    for f, v in enumerate(link_verts):
+        if v is None:
+            v = torch.zeros((0, 3), dtype=torch.float32, device=device)
+        _require_device(v, "link_verts[%d]" % f)
+        if v.dim() != 2 or v.shape[1] != 3:
+            raise PntfError("link_verts[%d] must be (v, 3), got %s" % (f, tuple(v.shape)))
+        if v.device != device:
+            raise PntfError("link_verts and theta must be on the same device")
+        parts.append(v.detach().to(torch.float32))
+        voff[f + 1] = voff[f] + v.shape[0]
+    if voff[-1] > 0x7fffffff:
+        raise PntfError("too many link vertices")
+    return torch.cat(parts).contiguous(), voff.astype(np.int32)
+
+
+def arm_mesh_distance(theta, chain, link_verts, tris, cap=None):
+    """Minimum distance (n,) from the collision vertices of an arm posed at each joint vector
+    theta (n, chain.dof) to the triangle mesh tris (t, 3, 3) or (1, t, 3, 3), on the HIP
+    kernel (pntf_arm_mesh_distance) — what arm_obstacle_distance returns
+    (dataprocessing/speed_sampling_gpu.py:153-218).  `chain` is a kin.SerialChain;
+    `link_verts` its links' vertices in link-local coordinates, a dict link name -> (v, 3)
+    tensor (links without an entry own none) or a list aligned with the frames.  `cap` bounds
+    the result (min(cap, distance), the same bits) and lets the kernel skip triangles farther
+    than that; None = exact."""
+    _require_device(theta, "theta")
+    _require_device(tris, "tris")
+    if theta.dim() != 2 or theta.shape[1] != chain.dof:
+        raise PntfError("theta must be (n, %d), got %s" % (chain.dof, tuple(theta.shape)))
+    tris = tris.reshape(-1, 3, 3) if tris.dim() == 4 and tris.shape[0] == 1 else tris
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3):
+        raise PntfError("tris must be (t, 3, 3) or (1, t, 3, 3), got %s" % (tuple(tris.shape),))
+    if theta.device != tris.device:
+        raise PntfError("theta and tris must be on the same device")
+    verts, voff = _link_vertices(chain, link_verts, theta.device)
+    theta = theta.detach().to(torch.float32).contiguous()
+    tris = tris.detach().to(torch.float32).contiguous()
+    out = torch.empty(theta.shape[0], dtype=torch.float32, device=theta.device)
+    if theta.shape[0] == 0:
+        return out
+    host = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(_lib.load().pntf_arm_mesh_distance(
+        _vp(theta), theta.shape[0], chain.dof, len(chain.link_names), host(chain.origins),
+        host(chain.types), host(chain.axes), host(chain.cols), _vp(verts), host(voff),
+        _vp(tris), tris.shape[0], float("inf") if cap is None else float(cap), _vp(out),
+        _stream(theta.device)), "pntf_arm_mesh_distance")
     return out

@@ -419,6 +419,24 @@ int pntf_arm_mesh_distance(const float* theta, int64_t n, int dof, int frames,
                            const float* tris, int64_t t, float cap, float* dist,
                            hipStream_t stream);
 
+/* ---- Planned-path clearance (pntf_path.hip) -------------------------------------------- */
+
+/* For each of q polylines, the minimum unsigned distance from any of its segments to the mesh.
+ * pts (q, L, 3) device: polyline c uses its first cnt[c] points (cnt device int32, 0..L; a
+ * value outside is clamped); segment i joins points i and i+1, i < cnt[c]-1.  cnt 1 = a single
+ * point (point distance, the bits of pntf_point_mesh_distance); cnt 0 = dist +inf (or cap),
+ * where -1.  tris (t, 3, 3).  cap >= 0 (INFINITY = exact): dist[c] = min(cap, exact) bit for
+ * bit.  where[c] (may be NULL) = lowest segment index whose distance equals the minimum (0 for
+ * a single point; -1 if empty or the cap decided; unspecified between the two when the exact
+ * distance equals a finite cap > 0 to the bit).  A segment that pierces a triangle gives
+ * exactly 0.  The bits depend neither on L, nor on the chunking, nor on the other rows.
+ * ws: pntf_polyline_workspace_bytes(q) bytes, 8-byte aligned.  At most 65535 chunks of 1024
+ * segments per polyline.  Errors via pntf_mesh_last_error. */
+int pntf_polyline_mesh_distance(const float* pts, int64_t q, int32_t L, const int32_t* cnt,
+                                const float* tris, int64_t t, float cap, float* dist,
+                                int32_t* where, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t pntf_polyline_workspace_bytes(int64_t q);
+
 #ifdef __cplusplus
 }
 #endif

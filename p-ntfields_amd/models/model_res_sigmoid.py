@@ -330,6 +330,25 @@ class Model:
         return ops.plan(self.network.packed(), XP, self.network._B(XP.device), None, self.dim,
                         step, tol, max_iter, ops.GRAD_EXACT)
 
+    def PlanReport(self, path, steps, chain, link_verts, tris, tol=0.03, safety=0.0,
+                   resolution=0.05):
+        """Report on the joint-space paths `Plan` returned (pntf.evaluate.path_report):
+        converged, length (in the planner's normalised joint coordinates), clearance, where,
+        success = converged & (clearance > safety) and success_rate.  The clearance is SAMPLED,
+        not exact: every segment of the polyline (start side + reversed goal side) is
+        subdivided linearly in joint space so that no joint moves more than `resolution`
+        radians between samples, the samples are scaled by π/0.5 as in test/arm_plan.py, and
+        the clearance is the minimum of ops.arm_mesh_distance (collision vertices of `chain`'s
+        links, `link_verts`, against the mesh `tris`) over them; `where` is the segment of the
+        minimising sample.  The arm may come closer than that between two samples."""
+        from pntf import evaluate
+        path, steps = path.to(self._dev()), steps.to(self._dev())
+        pts, cnt = ops.plan_polylines(path, steps)
+        clearance, where = evaluate.arm_path_clearance(pts, cnt, chain, link_verts,
+                                                       tris.to(self._dev()), resolution)
+        return evaluate.path_report(path, steps, tol, safety=safety, clearance=clearance,
+                                    where=where)
+
     def field_grid(self, limit=2.0):
         """The 80x80 evaluation grid of Model.plot (:1284-1311): start fixed at the reference's
         joint configuration Xsrc/(π/0.5), goal swept over [-limit, limit)^2 in the first two

@@ -369,6 +369,20 @@ class Model:
         return ops.plan(self.network.packed(), XP, _as_table(B, XP.device), env, self.dim,
                         step, tol, max_iter, mode)
 
+    def PlanReport(self, path, steps, tris, tol=0.06, safety=0.0):
+        """Report on the paths `Plan` returned (pntf.evaluate.path_report): per query whether
+        it converged (final |x_g - x_s| <= tol), its length, its exact clearance from the
+        obstacle mesh tris (t, 3, 3) — the minimum segment -> triangle distance of the polyline
+        start side + reversed goal side, on the HIP kernel (ops.polyline_mesh_distance) — the
+        segment of that minimum and success = converged & (clearance > safety); and the batch's
+        success_rate.  Workspace planning only (dim 3)."""
+        from pntf import evaluate
+        if self.dim != 3:
+            raise ops.PntfError("PlanReport measures the path against a mesh in the workspace: "
+                                "dim must be 3")
+        return evaluate.path_report(path.to(self._dev()), steps.to(self._dev()), tol,
+                                    tris=tris.to(self._dev()), safety=safety)
+
     def field_grid(self, limit=0.5):
         """The 80x80 evaluation grid of Model.plot (:1250-1275): start fixed at
         (-0.25, -0.25, 0, ...), goal swept over [-limit, limit)^2 in the first two axes;

@@ -136,6 +136,12 @@ SIGNATURES = {
                                               _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                               _c_void_p, _c_void_p, _c_void_p, _i64, _f32,
                                               _c_void_p, _c_void_p]),
+    # planned-path clearance (pntf_path.hip): pts, q, L, cnt, tris, t, cap, dist, where, ws,
+    # ws_bytes, stream
+    "pntf_polyline_mesh_distance": (ctypes.c_int, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p,
+                                                   _i64, _f32, _c_void_p, _c_void_p, _c_void_p,
+                                                   _size, _c_void_p]),
+    "pntf_polyline_workspace_bytes": (_size, [_i64]),
 }
 
 _lib = None
@@ -176,7 +182,7 @@ def check(status, what):
         lib = load()
         if what.startswith(("pntf_tt_", "pntf_adamw")):
             err = lib.pntf_tt_last_error()
-        elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh")):
+        elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh", "pntf_polyline_mesh")):
             err = lib.pntf_mesh_last_error()
         else:
             err = lib.pntf_last_error()

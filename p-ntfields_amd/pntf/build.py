@@ -159,7 +159,8 @@ UNITS = (
        for d in (3, 6)]
     + [("util", "pntf_kernels.hip", ["-DPNTF_UTIL"]), ("capi", "pntf_capi.hip", []),
        ("train", "pntf_train.hip", []), ("gemm", "pntf_gemm.hip", []),
-       ("mesh", "pntf_mesh.hip", []), ("arm", "pntf_arm.hip", [])]
+       ("mesh", "pntf_mesh.hip", []), ("arm", "pntf_arm.hip", []),
+       ("path", "pntf_path.hip", [])]
 )
 
 

@@ -1,0 +1,137 @@
+"""Evaluation of planned paths: did the planner converge, how long is the path, and does it
+stay clear of the obstacle mesh — the success rate NTFields results are judged by, which the
+reference's own scripts leave to an open3d viewer (test/gib_plan.py:92-109, test/arm_plan.py).
+
+`path_report` works on the output of `ops.plan` / `Model.Plan`.  In workspace planning (dim 3)
+the clearance is exact: the minimum segment -> triangle distance of the path's polyline on the
+HIP kernel (ops.polyline_mesh_distance), so a step through a thin wall counts as a collision
+even when both its ends are clear.  For the arm (joint space) the clearance is SAMPLED:
+`arm_path_samples` subdivides every segment linearly in joint space and
+`arm_path_clearance` takes the minimum of ops.arm_mesh_distance over the samples.
+"""
+import dataclasses
+import math
+
+import torch
+
+from . import ops
+from ._lib import PntfError
+
+ARM_SCALE = math.pi / 0.5     # normalised joint coordinates -> radians (test/arm_plan.py)
+
+
+@dataclasses.dataclass
+class PathReport:
+    """Per-query tensors (q,) and the batch's success rate."""
+    converged: torch.Tensor     # bool: final |x_g - x_s| <= tol
+    length: torch.Tensor        # float64: summed segment lengths of the polyline
+    clearance: torch.Tensor     # float32: minimum distance to the mesh (inf for an empty path)
+    where: torch.Tensor         # int32: segment of the minimum (-1: none)
+    success: torch.Tensor       # bool: converged & (clearance > safety)
+    success_rate: float         # mean of success (nan for an empty batch)
+
+
+def polyline_length(pts, cnt):
+    """Summed segment lengths (q,) float64 of the polylines pts (q, L, dim), cnt (q,)."""
+    p = pts.to(torch.float64)
+    seg = (p[:, 1:] - p[:, :-1]).norm(dim=2)
+    j = torch.arange(seg.shape[1], device=pts.device)[None, :]
+    return (seg * (j < cnt.to(torch.int64)[:, None] - 1)).sum(dim=1)
+
+
+def path_report(path, steps, tol, *, tris=None, safety=0.0, cap=None, clearance=None,
+                where=None):
+    """Report on planned paths: path (q, max_iter + 2, 2·dim), steps (q,) as `ops.plan` returns
+    them, `tol` the planner's tolerance.
+
+      converged   final |x_g - x_s| <= tol, read from the last valid row path[c, steps[c]] (not
+                  from steps: a query that used all its iterations may or may not have arrived);
+                  False for steps -1 (invalid env)
+      length      length of the polyline ops.plan_polylines builds (start side, junction, goal
+                  side), accumulated in fp64
+      clearance   minimum distance from the polyline's segments to the mesh `tris` (dim 3 only:
+                  ops.polyline_mesh_distance, exact), or the `clearance` (and `where`) given by
+                  the caller, e.g. the arm's sampled one (arm_path_clearance)
+      where       segment index of that minimum, -1 if there is none
+      success     converged & (clearance > safety)
+
+    `cap` is passed to the kernel (distances above it are reported as cap); it must exceed
+    `safety` to leave `success` unchanged."""
+    if path.dim() != 3 or path.shape[2] % 2:
+        raise PntfError("path must be (q, rows, 2·dim), got %s" % (tuple(path.shape),))
+    q, dim = path.shape[0], path.shape[2] // 2
+    pts, cnt = ops.plan_polylines(path, steps)
+    s = steps.to(device=path.device, dtype=torch.int64)
+    final = path.gather(1, s.clamp(min=0)[:, None, None].expand(q, 1, 2 * dim))[:, 0]
+    converged = ((final[:, dim:] - final[:, :dim]).norm(dim=1) <= tol) & (s >= 0)
+    if clearance is None:
+        if tris is None:
+            raise PntfError("path_report needs the mesh `tris` or a `clearance`")
+        if dim != 3:
+            raise PntfError("the mesh clearance of a path is defined for dim 3 (workspace "
+                            "planning); pass the arm's sampled clearance (arm_path_clearance)")
+        if cap is not None and not cap > safety:
+            raise PntfError("cap must exceed safety")
+        clearance, where = ops.polyline_mesh_distance(pts, cnt, tris, cap=cap)
+    else:
+        clearance = clearance.to(path.device)
+        if clearance.shape != (q,):
+            raise PntfError("clearance must be (q,), got %s" % (tuple(clearance.shape),))
+        if where is None:
+            where = torch.full((q,), -1, dtype=torch.int32, device=path.device)
+    success = converged & (clearance > safety)
+    rate = float(success.to(torch.float64).mean()) if q else float("nan")
+    return PathReport(converged, polyline_length(pts, cnt), clearance, where, success, rate)
+
+
+def arm_path_samples(pts, cnt, resolution, scale=ARM_SCALE):
+    """Joint-space samples of the polylines pts (q, L, dof) (normalised coordinates), cnt (q,):
+    every segment is subdivided linearly into ceil(max_j |Δθ_j| / resolution) pieces (at least
+    one), Δθ in radians (= scale · Δ), so no joint moves more than `resolution` between
+    consecutive samples; each piece contributes its first point and every polyline its last
+    point.  Returns (theta (n, dof) radians, query (n,) int64, segment (n,) int64), ordered by
+    query, then along the path; the last point belongs to the last segment."""
+    if not resolution > 0:
+        raise PntfError("resolution must be > 0 radians")
+    q, L, dof = pts.shape
+    dev = pts.device
+    cnt = cnt.to(device=dev, dtype=torch.int64)
+    delta = pts[:, 1:] - pts[:, :-1]                                    # (q, L-1, dof)
+    move = delta.abs().amax(dim=2).to(torch.float64) * scale
+    pieces = torch.ceil(move / resolution).clamp(min=1).to(torch.int64)
+    live = torch.arange(max(L - 1, 0), device=dev)[None, :] < cnt[:, None] - 1
+    pieces = pieces * live
+    flat = pieces.reshape(-1)
+    seg_id = torch.repeat_interleave(torch.arange(flat.numel(), device=dev), flat)
+    first = torch.cumsum(flat, 0) - flat
+    k = torch.arange(seg_id.numel(), device=dev) - first[seg_id]
+    frac = (k.to(torch.float64) / flat[seg_id].to(torch.float64)).to(pts.dtype)
+    qi, si = seg_id // max(L - 1, 1), seg_id % max(L - 1, 1)
+    theta = pts[qi, si] + frac[:, None] * delta.reshape(-1, dof)[seg_id]
+    # the last point of every non-empty polyline
+    has = torch.nonzero(cnt > 0)[:, 0]
+    theta = torch.cat([theta, pts[has, cnt[has] - 1]])
+    qi = torch.cat([qi, has])
+    si = torch.cat([si, (cnt[has] - 2).clamp(min=0)])
+    order = torch.argsort(qi, stable=True)
+    return theta[order] * scale, qi[order], si[order]
+
+
+def arm_path_clearance(pts, cnt, chain, link_verts, tris, resolution=0.05, scale=ARM_SCALE):
+    """SAMPLED clearance of joint-space polylines (not exact: the arm may come closer between
+    two samples): the minimum of ops.arm_mesh_distance over arm_path_samples(pts, cnt,
+    resolution), and the segment of the (first) minimising sample.  Returns (clearance (q,)
+    float32 — inf for an empty polyline — and where (q,) int32, -1 for an empty polyline)."""
+    q = pts.shape[0]
+    theta, qi, si = arm_path_samples(pts, cnt, resolution, scale)
+    d = ops.arm_mesh_distance(theta, chain, link_verts, tris)
+    clearance = torch.full((q,), float("inf"), dtype=torch.float32, device=pts.device)
+    clearance.scatter_reduce_(0, qi, d, "amin")
+    n = theta.shape[0]
+    idx = torch.where(d == clearance[qi], torch.arange(n, device=pts.device),
+                      torch.full((n,), n, device=pts.device))
+    firstmin = torch.full((q,), n, dtype=torch.int64, device=pts.device)
+    firstmin.scatter_reduce_(0, qi, idx, "amin")
+    where = torch.where(firstmin < n, si[firstmin.clamp(max=max(n - 1, 0))] if n else firstmin,
+                        torch.full_like(firstmin, -1))
+    return clearance, where.to(torch.int32)

@@ -21,7 +21,7 @@ from ._lib import GRAD_BACKGRAD_COMPAT, GRAD_EXACT, PntfError, check
 __all__ = ["GRAD_EXACT", "GRAD_BACKGRAD_COMPAT", "PntfError", "pack_weights", "tau",
            "tau_grad", "path_velocity", "speed", "travel_time", "plan", "eikonal_residual",
            "device_sum", "packed_floats", "workspace_bytes", "point_mesh_distance",
-           "arm_mesh_distance"]
+           "arm_mesh_distance", "polyline_mesh_distance", "plan_polylines"]
 
 class StreamScratch:
     """Grow-only device scratch per (device, stream), least-recently-used first out.
@@ -384,3 +384,69 @@ def arm_mesh_distance(theta, chain, link_verts, tris, cap=None):
         _vp(tris), tris.shape[0], float("inf") if cap is None else float(cap), _vp(out),
         _stream(theta.device)), "pntf_arm_mesh_distance")
     return out
+
+
+def polyline_mesh_distance(pts, cnt, tris, cap=None):
+    """Clearance of q polylines from the triangle mesh tris (t, 3, 3) or (1, t, 3, 3) on the HIP
+    kernel (pntf_polyline_mesh_distance): pts (q, L, 3), polyline c = its first cnt[c] points
+    (cnt (q,) integer, 0..L), joined in order.  Returns (dist (q,) float32, where (q,) int32):
+    the exact minimum over the polyline's SEGMENTS of the segment -> mesh distance — 0.0 where a
+    segment passes through a triangle even if both its ends are clear — and the lowest segment
+    index that attains it.  One point (cnt 1) gives the point distance with where 0; an empty
+    polyline (cnt 0) gives inf (or cap) and where -1.  `cap` bounds the result (min(cap,
+    distance), the same bits, where -1 if the cap decided) and lets the kernel skip triangles
+    farther than that; None = exact."""
+    _require_device(pts, "pts")
+    _require_device(cnt, "cnt")
+    _require_device(tris, "tris")
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise PntfError("pts must be (q, L, 3), got %s" % (tuple(pts.shape),))
+    if cnt.dim() != 1 or cnt.shape[0] != pts.shape[0] or cnt.is_floating_point():
+        raise PntfError("cnt must be (q,) integers, one per polyline, got %s %s"
+                        % (tuple(cnt.shape), cnt.dtype))
+    tris = tris.reshape(-1, 3, 3) if tris.dim() == 4 and tris.shape[0] == 1 else tris
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3):
+        raise PntfError("tris must be (t, 3, 3) or (1, t, 3, 3), got %s" % (tuple(tris.shape),))
+    if not (pts.device == cnt.device == tris.device):
+        raise PntfError("pts, cnt and tris must be on the same device")
+    lib = _lib.load()
+    pts = pts.detach().to(torch.float32).contiguous()
+    cnt = cnt.detach().to(torch.int32).contiguous()
+    tris = tris.detach().to(torch.float32).contiguous()
+    q, L = pts.shape[0], pts.shape[1]
+    dist = torch.empty(q, dtype=torch.float32, device=pts.device)
+    where = torch.empty(q, dtype=torch.int32, device=pts.device)
+    if q == 0:
+        return dist, where
+    ws = _ws_cache.get(pts.device, int(lib.pntf_polyline_workspace_bytes(q)))
+    check(lib.pntf_polyline_mesh_distance(
+        _vp(pts), q, L, _vp(cnt), _vp(tris), tris.shape[0],
+        float("inf") if cap is None else float(cap), _vp(dist), _vp(where), _vp(ws), ws.numel(),
+        _stream(pts.device)), "pntf_polyline_mesh_distance")
+    return dist, where
+
+
+def plan_polylines(path, steps):
+    """The planner's output as polylines: path (q, max_iter + 2, 2·dim) and steps (q,) of
+    `plan` -> (pts (q, 2·(max_iter + 2), dim), cnt (q,) int32).  Query c's polyline is its start
+    side path[c, 0..steps[c], :dim] followed by its goal side path[c, steps[c]..0, dim:] — the
+    reference's point0 + reversed(point1) (test/gib_plan.py:92-93) — 2·steps[c] + 2 points;
+    the junction between the two sides is a segment like any other.  steps -1 (invalid env)
+    gives cnt 0; rows past cnt are zero.  Pure indexing: runs on CPU tensors too."""
+    if path.dim() != 3 or path.shape[2] % 2 or steps.dim() != 1 or \
+            steps.shape[0] != path.shape[0]:
+        raise PntfError("path must be (q, rows, 2·dim) and steps (q,), got %s and %s"
+                        % (tuple(path.shape), tuple(steps.shape)))
+    q, rows, dim = path.shape[0], path.shape[1], path.shape[2] // 2
+    s = steps.to(device=path.device, dtype=torch.int64)
+    if q and int(s.max()) >= rows:
+        raise PntfError("steps exceeds the path's rows")
+    cnt = torch.where(s >= 0, 2 * s + 2, torch.zeros_like(s))
+    s = s.clamp(min=0)[:, None]
+    j = torch.arange(2 * rows, device=path.device)[None, :]
+    first = j <= s
+    row = torch.where(first, j, 2 * s + 1 - j).clamp(0, rows - 1)
+    src = path.gather(1, row[:, :, None].expand(q, 2 * rows, 2 * dim))
+    pts = torch.where(first[:, :, None], src[:, :, :dim], src[:, :, dim:])
+    pts = pts * (j < cnt[:, None])[:, :, None]
+    return pts.contiguous(), cnt.to(torch.int32)

@@ -109,7 +109,18 @@ const char* pntf_build_info(void);
  * WAVE_TILE. */
 int pntf_field_schedule_for(int64_t n, int schedule);
 
-/* Device scratch needed by the gradient/planner entry points for n pairs. */
+/* Device scratch needed by the gradient/planner entry points for n pairs: enough for the
+ * widest grid any schedule launches for n.  A call accepts less, down to one workgroup's
+ * scratch of the kernel family it runs (one slot of saved activations per wave):
+ *   WAVE_TILE field kernels, the WAVE_TILE planner, pntf_eikonal_residual    786 432 bytes
+ *   SPLIT_TILE field kernels and planner                                   1 572 864 bytes
+ *   WIDE_TILE field kernels                                                1 572 864 bytes
+ * (pntf_workspace_bytes(1) is the largest of the three).  ws_bytes / that size, rounded
+ * down, caps the number of workgroups; below one, PNTF_ERR_WORKSPACE.  Nothing at or past
+ * ws + ws_bytes is touched.  Results do not depend on ws_bytes: a pair's or query's outputs
+ * have the same bits whichever workgroup computes them.  QUAD_TILE kernels, PNTF_FIELD_TAU and
+ * PNTF_FIELD_TRAVEL take no scratch (ws may be NULL); the AUTO planner's tail hand-off uses
+ * the first 8 + 8q bytes when ws holds that many and is skipped otherwise. */
 size_t pntf_workspace_bytes(int64_t n);
 
 /* τ only: NN.out / Model.Tau (model_res_sigmoid_multi.py:215-259, :1188-1193). tau (n). */

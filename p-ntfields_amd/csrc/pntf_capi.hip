@@ -125,9 +125,15 @@ static bool use_quad(int64_t n, int schedule) {
 static int grid_with_ws(int64_t n, size_t ws_bytes, int64_t* grid, bool split = false,
                         bool wide = false) {
   int64_t g = split ? split_grid_for(n) : wide ? wide_grid_for(n) : grid_for(n);
-  int64_t fit = (int64_t)(ws_bytes / ((wide ? WSLOT_BYTES : SLOT_BYTES) *
-                                      (split ? SPLIT_WAVES : WAVES)));
-  if (fit < 1) return fail(PNTF_ERR_WORKSPACE, "workspace too small (%s)", "need >= 4 slots");
+  // one workgroup's scratch: a slot per wave (include/pntf.h, pntf_workspace_bytes)
+  const size_t wg_bytes = (wide ? WSLOT_BYTES : SLOT_BYTES) * (split ? SPLIT_WAVES : WAVES);
+  int64_t fit = (int64_t)(ws_bytes / wg_bytes);
+  if (fit < 1) {
+    snprintf(g_err, sizeof(g_err),
+             "workspace too small: %zu bytes, the %s kernels need >= %zu (one workgroup's scratch)",
+             ws_bytes, split ? "split-tile" : wide ? "wide-tile" : "wave-tile", wg_bytes);
+    return PNTF_ERR_WORKSPACE;
+  }
   *grid = g < fit ? g : fit;
   return PNTF_OK;
 }

@@ -604,7 +604,7 @@ __global__ __launch_bounds__(64 * SPLIT, 1) void field_split_kernel(FieldArgs a)
 
 // Batched planner on split tiles: one workgroup per 16-query tile (grid-stride), the loop of
 // plan_kernel (test/gib_plan.py:74-86, test/arm_plan.py:140-152) with per-query freeze.
-// ws holds one scratch slot per wave (4 per workgroup).
+// ws holds one scratch slot per wave (SPLIT per workgroup).
 template <int DIM>
 __global__ __launch_bounds__(64 * SPLIT, 1) void plan_split_kernel(PlanArgs a) {
   __shared__ float smem[SPLIT_LDS_FLOATS];

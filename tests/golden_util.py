@@ -179,3 +179,25 @@ def north_star_pairs(what, got, ref, f64, tol=NORTH_STAR, diff=False):
     assert not bad, "%s: pairs off by >= %.0e from both the golden and fp64: %s" % (
         what, tol, bad[:8])
     return (float(e.max()) if e.size else 0.0), adj
+
+
+# ---- the parity bounds of the GPU tests (tests/test_gpu_parity.py module docstring)
+REL = 1e-4
+ELEM = 1e-3
+ELEM_FLOOR = 1e-2
+
+
+def close(a, b, tol=REL, elem=ELEM, pairs=False, diff=False):
+    """Normwise and elementwise bounds (module docstring); pairs=True adds the north star per
+    pair against `b`, which is then the fp64 oracle itself (diff: the Eikonal residual,
+    relative to |diff| + 4)."""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64)
+    l2 = rel_l2(a, b)
+    scale = max(np.abs(b).max(), 1e-30)
+    mx = float(np.abs(a - b).max() / scale)
+    el = max_rel(a, b, ELEM_FLOOR * scale)
+    assert l2 < tol and mx < tol and el < elem, \
+        "rel_l2=%.3g max=%.3g elementwise=%.3g (tol %.1g, elem %.1g)" % (l2, mx, el, tol, elem)
+    if pairs:
+        north_star_pairs("vs fp64 oracle", a, b, b, diff=diff)

@@ -13,31 +13,12 @@ import numpy as np
 import pytest
 import torch
 
-from golden_util import fp64_of, load, max_rel, north_star_pairs, rel_l2, weights
+from golden_util import (ELEM_FLOOR, close, fp64_of, load, max_rel, north_star_pairs, rel_l2,
+                         weights)
 from oracle import pntf_oracle as O
 from pntf import ops, synth
 
 pytestmark = pytest.mark.gpu
-
-REL = 1e-4
-ELEM = 1e-3
-ELEM_FLOOR = 1e-2
-
-
-def close(a, b, tol=REL, elem=ELEM, pairs=False, diff=False):
-    """Normwise and elementwise bounds (module docstring); pairs=True adds the north star per
-    pair against `b`, which is then the fp64 oracle itself (diff: the Eikonal residual,
-    relative to |diff| + 4)."""
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    l2 = rel_l2(a, b)
-    scale = max(np.abs(b).max(), 1e-30)
-    mx = float(np.abs(a - b).max() / scale)
-    el = max_rel(a, b, ELEM_FLOOR * scale)
-    assert l2 < tol and mx < tol and el < elem, \
-        "rel_l2=%.3g max=%.3g elementwise=%.3g (tol %.1g, elem %.1g)" % (l2, mx, el, tol, elem)
-    if pairs:
-        north_star_pairs("vs fp64 oracle", a, b, b, diff=diff)
 
 
 def check(got, name, key, **kw):

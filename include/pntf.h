@@ -448,6 +448,54 @@ int pntf_polyline_mesh_distance(const float* pts, int64_t q, int32_t L, const in
                                 int32_t* where, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t pntf_polyline_workspace_bytes(int64_t q);
 
+/* ---- Grid travel time (pntf_eikonal.hip) ----------------------------------------------- */
+
+/* The true travel time T(x_s, .) of a speed field is the viscosity solution of the Eikonal
+ * equation |grad T| = 1 / S.  These two entry points compute its first-order upwind
+ * discretisation on a grid, for q sources at once (not in the reference: what a model's
+ * TravelTimes is measured against, p-ntfields_amd/pntf/evaluate.py field_report).
+ *
+ * Grid: n^3 nodes, n >= 2; node (i, j, k) sits at x = -0.5 + h (i, j, k), h = 1 / (n - 1);
+ * arrays are (n, n, n), k fastest.  `speed` (n, n, n) is S at the nodes, shared by all
+ * sources; a node with S <= 0 (or NaN) is a wall and keeps T = +inf.  f = h / S.
+ *
+ * One update of a node:
+ *   a <= b <= c the sorted per-axis minima of its two neighbours' T (outside the grid: +inf);
+ *   t = a + f                                                    (+inf when a is);
+ *   if b is finite and t > b:  t = (a + b + sqrt(max(2 f^2 - (a - b)^2, 0))) / 2;
+ *   if then c is finite and t > c, with s = a + b + c:
+ *                              t = (s + sqrt(max(s^2 - 3 (a^2 + b^2 + c^2 - f^2), 0))) / 3;
+ *   T <- min(T, t).
+ * The answer is the fixed point of updating every node from the previous values (Jacobi): the
+ * iteration only lowers values, so it gets there in finitely many steps, and the fixed point
+ * is the fast-marching solution.
+ *
+ * pntf_grid_travel_time_init fills T (q, n, n, n) for the sources src (q, 3), points of the
+ * box: +inf everywhere, except that the node nearest the source (per axis
+ * floor((x_s + 0.5)(n - 1) + 0.5), clamped to the grid) and every node with
+ * |x - x_s|^2 <= (radius h)^2 get |x - x_s| / S_near, S_near the speed at that nearest node.
+ * Walls stay +inf; a source whose nearest node is a wall leaves every node +inf.  The
+ * geometry is evaluated in fp64 (node coordinates, distances and the ball test), the quotient
+ * in fp32.  radius 0 starts from the nearest node alone.
+ *
+ * pntf_grid_travel_time_pass advances every source by one pass: each 8x8x8 tile of the grid
+ * takes its nodes and a one-node halo from Tin, runs `inner` >= 1 update sweeps of its own
+ * nodes with the halo held fixed, and writes its nodes to Tout.  Tin and Tout (q, n, n, n)
+ * must be distinct buffers (ping-pong): the state after p passes is then a pure function of
+ * speed, src, radius, n, inner and p — the same bits run to run, whatever the other sources of
+ * the batch.  changed (q) int32 is ACCUMULATED: changed[c] += the number of tiles of source c
+ * that lowered any node in this pass.  The caller zeroes it, launches a few passes, reads it,
+ * and stops when it reads 0: a pass that changes nothing has reached the fixed point (for any
+ * `inner`: values never rise, so a pass changes nothing only if its first sweep did).
+ *
+ * Limits: ceil(n/8)^3 * 512 < 2^32 (n <= 1624) and q <= 65535.  Errors via
+ * pntf_mesh_last_error. */
+int pntf_grid_travel_time_init(const float* speed, int32_t n, const float* src, int64_t q,
+                               float radius, float* T, hipStream_t stream);
+int pntf_grid_travel_time_pass(const float* speed, int32_t n, int64_t q, const float* Tin,
+                               float* Tout, int32_t inner, int32_t* changed,
+                               hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

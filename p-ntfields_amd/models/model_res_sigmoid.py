@@ -349,6 +349,13 @@ class Model:
         return evaluate.path_report(path, steps, tol, safety=safety, clearance=clearance,
                                     where=where)
 
+    def FieldReport(self, *args, **kwargs):
+        """The field report (pntf.evaluate.field_report) compares the field with a grid Eikonal
+        solve of a mesh's speed field in the workspace; in joint space there is no such grid,
+        so the arm model raises, as the multi model does at dim != 3."""
+        raise ops.PntfError("FieldReport measures the field against a mesh in the workspace "
+                            "(dim 3): not defined for the arm model")
+
     def field_grid(self, limit=2.0):
         """The 80x80 evaluation grid of Model.plot (:1284-1311): start fixed at the reference's
         joint configuration Xsrc/(π/0.5), goal swept over [-limit, limit)^2 in the first two

@@ -383,6 +383,24 @@ class Model:
         return evaluate.path_report(path.to(self._dev()), steps.to(self._dev()), tol,
                                     tris=tris.to(self._dev()), safety=safety)
 
+    def FieldReport(self, tris, sources, n=65, offset=None, margin=None, radius=4.0):
+        """How far this model's field is from the true travel time of the scene `tris`
+        (t, 3, 3) (pntf.evaluate.field_report): for each start point of `sources` (q, 3), the
+        relative error of TravelTimes (uses self.B) against a grid Eikonal solve of the mesh's
+        speed field on n^3 nodes (ops.grid_travel_time), the absolute error of Speed against
+        that exact speed field, and the grid solve's own discretisation error (floor_*).  A
+        travel-time error below the floor is not resolved at that n.  offset / margin default
+        to the reference's Gibson values (margin 0.5/12, offset margin/10).  Runs under no_grad
+        on the fused kernels.  Workspace models only (dim 3)."""
+        from pntf import evaluate
+        if self.dim != 3:
+            raise ops.PntfError("FieldReport measures the field against a mesh in the "
+                                "workspace: dim must be 3")
+        with torch.no_grad():
+            return evaluate.field_report(self.TravelTimes, self.Speed, tris.to(self._dev()),
+                                         sources.to(self._dev()), n=n, offset=offset,
+                                         margin=margin, radius=radius)
+
     def field_grid(self, limit=0.5):
         """The 80x80 evaluation grid of Model.plot (:1250-1275): start fixed at
         (-0.25, -0.25, 0, ...), goal swept over [-limit, limit)^2 in the first two axes;

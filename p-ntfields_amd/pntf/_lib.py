@@ -142,6 +142,12 @@ SIGNATURES = {
                                                    _i64, _f32, _c_void_p, _c_void_p, _c_void_p,
                                                    _size, _c_void_p]),
     "pntf_polyline_workspace_bytes": (_size, [_i64]),
+    # grid travel time (pntf_eikonal.hip): speed, n, src, q, radius, T, stream /
+    # speed, n, q, Tin, Tout, inner, changed, stream
+    "pntf_grid_travel_time_init": (ctypes.c_int, [_c_void_p, _i32, _c_void_p, _i64, _f32,
+                                                  _c_void_p, _c_void_p]),
+    "pntf_grid_travel_time_pass": (ctypes.c_int, [_c_void_p, _i32, _i64, _c_void_p, _c_void_p,
+                                                  _i32, _c_void_p, _c_void_p]),
 }
 
 _lib = None
@@ -182,7 +188,8 @@ def check(status, what):
         lib = load()
         if what.startswith(("pntf_tt_", "pntf_adamw")):
             err = lib.pntf_tt_last_error()
-        elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh", "pntf_polyline_mesh")):
+        elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh", "pntf_polyline_mesh",
+                              "pntf_grid_travel_time")):
             err = lib.pntf_mesh_last_error()
         else:
             err = lib.pntf_last_error()

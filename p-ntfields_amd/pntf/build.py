@@ -160,7 +160,7 @@ UNITS = (
     + [("util", "pntf_kernels.hip", ["-DPNTF_UTIL"]), ("capi", "pntf_capi.hip", []),
        ("train", "pntf_train.hip", []), ("gemm", "pntf_gemm.hip", []),
        ("mesh", "pntf_mesh.hip", []), ("arm", "pntf_arm.hip", []),
-       ("path", "pntf_path.hip", [])]
+       ("path", "pntf_path.hip", []), ("eikonal", "pntf_eikonal.hip", [])]
 )
 
 
@@ -210,7 +210,8 @@ def _resources(stderr):
             cur = out.setdefault(m.group(1), {})
             continue
         m = re.search(r"remark:.*?\s(VGPRs|AGPRs|TotalSGPRs|VGPRs Spill|SGPRs Spill|"
-                      r"ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+) ", line)
+                      r"ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
+                      r"LDS Size \[bytes/block\]): (\d+) ", line)
         if m and cur is not None:
             cur[m.group(1)] = int(m.group(2))
     return out

@@ -8,6 +8,11 @@ HIP kernel (ops.polyline_mesh_distance), so a step through a thin wall counts as
 even when both its ends are clear.  For the arm (joint space) the clearance is SAMPLED:
 `arm_path_samples` subdivides every segment linearly in joint space and
 `arm_path_clearance` takes the minimum of ops.arm_mesh_distance over the samples.
+
+`field_report` judges the FIELD instead of a path: the model's TravelTimes and Speed at the
+nodes of a grid over the box against the scene's ground truth — the speed from the exact
+point -> mesh distance, and the travel time from a grid Eikonal solve of that speed
+(ops.grid_travel_time) — together with the solver's own discretisation error at that grid.
 """
 import dataclasses
 import math
@@ -82,6 +87,87 @@ def path_report(path, steps, tol, *, tris=None, safety=0.0, cap=None, clearance=
     success = converged & (clearance > safety)
     rate = float(success.to(torch.float64).mean()) if q else float("nan")
     return PathReport(converged, polyline_length(pts, cnt), clearance, where, success, rate)
+
+
+GIBSON_MARGIN = 0.5 / 12.0    # dataprocessing/speed_sampling_gpu.py:470-472; offset = margin / 10
+
+
+@dataclasses.dataclass
+class FieldReport:
+    """Per-source tensors (q,) on the device, and the two grids they were taken on."""
+    converged: torch.Tensor       # bool: the grid solve reached its fixed point
+    passes: torch.Tensor          # int32: passes of the grid solve
+    tt_mean_rel: torch.Tensor     # float64: mean |T_model - T_grid| / T_grid
+    tt_max_rel: torch.Tensor      # float64: max of the same
+    speed_mean_abs: torch.Tensor  # float64: mean |Speed - speed grid| over all nodes
+    speed_max_abs: torch.Tensor   # float64: max of the same
+    floor_mean_rel: torch.Tensor  # float64: the solver's own mean relative error at this n
+    floor_max_rel: torch.Tensor   # float64: max of the same
+    T_grid: torch.Tensor          # float32 (q, n, n, n): the grid travel times
+    speed: torch.Tensor           # float32 (n, n, n): the ground-truth speed at the nodes
+
+
+def field_report(travel_times, speed, tris, sources, n=65, offset=None, margin=None, radius=4.0):
+    """How far a model's field is from the true travel time of a scene.  `travel_times` and
+    `speed` are the model's epilogues (callables on (N, 6) pairs [x_start | x_goal] returning
+    (N,) or (N, 1): Model.TravelTimes and Model.Speed), `tris` (t, 3, 3) the obstacle mesh,
+    `sources` (q, 3) start points in the box [-0.5, 0.5]^3.  dim 3 only.
+
+    Ground truth: the speed the samplers label points with, clip(d, offset, margin) / margin
+    (ops.speed_grid; defaults: the reference's Gibson values margin = 0.5/12, offset =
+    margin/10), at the n^3 nodes of the box, and T_grid = ops.grid_travel_time of that speed
+    from each source: the first-order upwind Eikonal solution, initialised exactly within
+    `radius` nodes of the source.  Per source:
+
+      converged, passes          of the grid solve
+      tt_mean_rel, tt_max_rel    |T_model - T_grid| / T_grid, T_model = travel_times from the
+                                 source to every node, over the nodes outside the initial ball
+                                 whose T_grid is finite
+      speed_mean_abs, _max_abs   |speed(source -> node) - speed grid| over all nodes; the speed
+                                 grid is exact, so this row has no resolution limit
+      floor_mean_rel, _max_rel   the solver's own discretisation error at this n: a second solve
+                                 with speed 1 everywhere, same source and radius, against
+                                 |x - x_s|, relative, over the same nodes as the tt rows
+
+    T_grid is itself a first-order approximation, a few percent off at n = 33..65 (the floor_*
+    rows measure it in free space): a travel-time error BELOW THE FLOOR IS NOT RESOLVED at this
+    n — raise n, do not read it as model error.  Rows over an empty node set are nan."""
+    _require = ops._require_device
+    _require(tris, "tris")
+    _require(sources, "sources")
+    if sources.dim() != 2 or sources.shape[1] != 3 or sources.shape[0] < 1:
+        raise PntfError("sources must be (q, 3) with q >= 1 (the field report is defined for "
+                        "dim 3), got %s" % (tuple(sources.shape),))
+    margin = GIBSON_MARGIN if margin is None else float(margin)
+    offset = margin / 10.0 if offset is None else float(offset)
+    dev, n = tris.device, int(n)
+    src = sources.detach().to(device=dev, dtype=torch.float32).contiguous()
+    q = src.shape[0]
+    S = ops.speed_grid(tris, n, offset, margin)
+    T, passes, converged = ops.grid_travel_time(S, src, radius=radius)
+    ones = torch.ones_like(S)
+    U, _, _ = ops.grid_travel_time(ones, src, radius=radius)
+    outside = ~torch.isfinite(ops.grid_travel_time_init(ones, src, radius)).reshape(q, -1)
+    nodes = ops.grid_nodes(n, dev)
+    rows = {k: torch.full((q,), float("nan"), dtype=torch.float64, device=dev)
+            for k in ("tt_mean_rel", "tt_max_rel", "speed_mean_abs", "speed_max_abs",
+                      "floor_mean_rel", "floor_max_rel")}
+    for c in range(q):
+        xp = torch.cat([src[c].expand(n ** 3, 3), nodes], dim=1).contiguous()
+        with torch.no_grad():
+            tm = travel_times(xp).reshape(-1).to(torch.float64)
+            sm = speed(xp).reshape(-1).to(torch.float64)
+        tg = T[c].reshape(-1).to(torch.float64)
+        m = outside[c] & torch.isfinite(tg)
+        es = (sm - S.reshape(-1).to(torch.float64)).abs()
+        rows["speed_mean_abs"][c], rows["speed_max_abs"][c] = es.mean(), es.max()
+        if bool(m.any()):
+            et = ((tm - tg).abs() / tg)[m]
+            dist = (nodes.to(torch.float64) - src[c].to(torch.float64)).norm(dim=1)
+            ef = ((U[c].reshape(-1).to(torch.float64) - dist).abs() / dist)[m]
+            rows["tt_mean_rel"][c], rows["tt_max_rel"][c] = et.mean(), et.max()
+            rows["floor_mean_rel"][c], rows["floor_max_rel"][c] = ef.mean(), ef.max()
+    return FieldReport(converged=converged, passes=passes, T_grid=T, speed=S, **rows)
 
 
 def arm_path_samples(pts, cnt, resolution, scale=ARM_SCALE):

@@ -21,7 +21,8 @@ from ._lib import GRAD_BACKGRAD_COMPAT, GRAD_EXACT, PntfError, check
 __all__ = ["GRAD_EXACT", "GRAD_BACKGRAD_COMPAT", "PntfError", "pack_weights", "tau",
            "tau_grad", "path_velocity", "speed", "travel_time", "plan", "eikonal_residual",
            "device_sum", "packed_floats", "workspace_bytes", "point_mesh_distance",
-           "arm_mesh_distance", "polyline_mesh_distance", "plan_polylines"]
+           "arm_mesh_distance", "polyline_mesh_distance", "plan_polylines", "grid_travel_time",
+           "grid_travel_time_init", "grid_travel_time_pass", "grid_nodes", "speed_grid"]
 
 class StreamScratch:
     """Grow-only device scratch per (device, stream), least-recently-used first out.
@@ -450,3 +451,126 @@ def plan_polylines(path, steps):
     pts = torch.where(first[:, :, None], src[:, :, :dim], src[:, :, dim:])
     pts = pts * (j < cnt[:, None])[:, :, None]
     return pts.contiguous(), cnt.to(torch.int32)
+
+
+def _grid_args(speed, what):
+    _require_device(speed, "speed")
+    if speed.dim() != 3 or not (speed.shape[0] == speed.shape[1] == speed.shape[2]) or \
+            speed.shape[0] < 2:
+        raise PntfError("%s: speed must be (n, n, n) with n >= 2, got %s"
+                        % (what, tuple(speed.shape)))
+    return speed.detach().to(torch.float32).contiguous()
+
+
+def _grid_sources(src, speed, what):
+    _require_device(src, "src")
+    if src.dim() == 1:
+        src = src[None]
+    if src.dim() != 2 or src.shape[1] != 3 or src.shape[0] < 1:
+        raise PntfError("%s: src must be (q, 3) with q >= 1, got %s" % (what, tuple(src.shape)))
+    if src.device != speed.device:
+        raise PntfError("%s: speed and src must be on the same device" % what)
+    return src.detach().to(torch.float32).contiguous()
+
+
+def grid_travel_time_init(speed, src, radius=4.0):
+    """Initial state T (q, n, n, n) of the grid solver (pntf_grid_travel_time_init): +inf, except
+    |x - x_s| / S_near at the node nearest each source and within radius·h of it."""
+    speed = _grid_args(speed, "grid_travel_time_init")
+    src = _grid_sources(src, speed, "grid_travel_time_init")
+    n, q = speed.shape[0], src.shape[0]
+    T = torch.empty((q, n, n, n), dtype=torch.float32, device=speed.device)
+    check(_lib.load().pntf_grid_travel_time_init(_vp(speed), n, _vp(src), q, float(radius),
+                                                  _vp(T), _stream(speed.device)),
+          "pntf_grid_travel_time_init")
+    return T
+
+
+def grid_travel_time_pass(speed, T, inner=8, changed=None):
+    """One pass of the grid solver on T (q, n, n, n) (pntf_grid_travel_time_pass): returns (a
+    new tensor with every 8x8x8 tile advanced by `inner` sweeps, changed (q,) int32).  `changed`
+    is accumulated into when given, else starts from zero."""
+    speed = _grid_args(speed, "grid_travel_time_pass")
+    _require_device(T, "T")
+    n = speed.shape[0]
+    if T.dim() != 4 or tuple(T.shape[1:]) != (n, n, n) or T.dtype != torch.float32 or \
+            not T.is_contiguous() or T.device != speed.device or T.shape[0] < 1:
+        raise PntfError("grid_travel_time_pass: T must be a contiguous float32 (q, %d, %d, %d) "
+                        "tensor on the speed's device" % (n, n, n))
+    q = T.shape[0]
+    if changed is None:
+        changed = torch.zeros(q, dtype=torch.int32, device=T.device)
+    elif changed.shape != (q,) or changed.dtype != torch.int32 or changed.device != T.device \
+            or not changed.is_contiguous():
+        raise PntfError("grid_travel_time_pass: changed must be (q,) int32 on T's device")
+    out = torch.empty_like(T)
+    check(_lib.load().pntf_grid_travel_time_pass(_vp(speed), n, q, _vp(T), _vp(out), int(inner),
+                                                  _vp(changed), _stream(T.device)),
+          "pntf_grid_travel_time_pass")
+    return out, changed
+
+
+def grid_travel_time(speed, src, radius=4.0, inner=8, check_every=4, max_passes=None):
+    """Travel time from each source src (q, 3) to every node of the n^3 grid of the unit box
+    under the speed field speed (n, n, n) (node (i, j, k) at -0.5 + (i, j, k) / (n - 1); a node
+    with speed <= 0 is a wall): the fixed point of the first-order upwind Eikonal scheme of
+    include/pntf.h, i.e. the fast-marching solution, on the HIP kernels.
+
+    Returns (T (q, n, n, n) float32 — +inf at walls and where no path leads —, passes (q,)
+    int32, converged (q,) bool).  The host launches `check_every` passes (each: `inner` sweeps
+    per 8x8x8 tile), reads the per-source change counters — the only synchronisation —, and
+    repeats until a whole interval changed nothing for every source or `max_passes` (default
+    8·n) passes have run; running out gives converged False, never an exception.  passes[c] is
+    the number of passes launched when source c's counter first read 0 (max_passes otherwise).
+    A converged T is the fixed point: its bits depend neither on check_every nor on the other
+    sources of the batch.  A non-finite speed raises PntfError."""
+    speed = _grid_args(speed, "grid_travel_time")
+    src = _grid_sources(src, speed, "grid_travel_time")
+    n, q = speed.shape[0], src.shape[0]
+    if int(check_every) < 1 or int(inner) < 1:
+        raise PntfError("grid_travel_time: inner and check_every must be >= 1")
+    max_passes = 8 * n if max_passes is None else int(max_passes)
+    if max_passes < 1:
+        raise PntfError("grid_travel_time: max_passes must be >= 1")
+    if not bool(torch.isfinite(speed).all()) or not bool(torch.isfinite(src).all()):
+        raise PntfError("grid_travel_time: speed and src must be finite")
+    lib, dev = _lib.load(), speed.device
+    cur = grid_travel_time_init(speed, src, radius)
+    nxt = torch.empty_like(cur)
+    changed = torch.zeros(q, dtype=torch.int32, device=dev)
+    passes = torch.full((q,), max_passes, dtype=torch.int32)
+    converged = torch.zeros(q, dtype=torch.bool)
+    done = 0
+    while done < max_passes:
+        for _ in range(min(int(check_every), max_passes - done)):
+            check(lib.pntf_grid_travel_time_pass(_vp(speed), n, q, _vp(cur), _vp(nxt),
+                                                 int(inner), _vp(changed), _stream(dev)),
+                  "pntf_grid_travel_time_pass")
+            cur, nxt = nxt, cur
+            done += 1
+        still = changed.cpu() == 0
+        changed.zero_()
+        passes[still & ~converged] = done
+        converged |= still
+        if bool(converged.all()):
+            break
+    return cur, passes.to(dev), converged.to(dev)
+
+
+def grid_nodes(n, device):
+    """Node coordinates (n^3, 3) float32 of the solver's grid, k fastest: -0.5 + (i, j, k) /
+    (n - 1), evaluated in fp64 and rounded once."""
+    ax = torch.arange(n, dtype=torch.float64, device=device) * (1.0 / (n - 1)) - 0.5
+    return torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), dim=-1).reshape(-1, 3).to(
+        torch.float32)
+
+
+def speed_grid(tris, n, offset, margin):
+    """Ground-truth speed (n, n, n) at the solver's nodes for the obstacle mesh tris (t, 3, 3):
+    clip(d, offset, margin) / margin with d = point_mesh_distance(nodes, tris) — the speed the
+    samplers label their points with (dataprocessing/speed_sampling_gpu.py:415-419)."""
+    _require_device(tris, "tris")
+    if int(n) < 2 or not (0 <= offset <= margin and margin > 0):
+        raise PntfError("speed_grid: need n >= 2 and 0 <= offset <= margin, margin > 0")
+    d = point_mesh_distance(grid_nodes(int(n), tris.device), tris)
+    return (d.clamp(float(offset), float(margin)) / float(margin)).reshape(n, n, n)

@@ -325,7 +325,14 @@ int pntf_tt_head_loss(int dim, int arm, const float* v, const float* w4, const f
  * weight streamed from L2, 2 = fp32 MFMA with the weight in LDS, 3 (default) = the split-bf16
  * kernel (every fp32 operand as three bf16 terms, six bf16 MFMA products per fp32 product:
  * fp32 accuracy at 2.67x the fp32 MFMA rate; 1.5*K*N work floats), 8 = its 16x16x32 variant
- * with two waves per SIMD (diagnostic; 4..7 are diagnostic forms of 3 as well). */
+ * with two waves per SIMD (diagnostic; 4..7 are diagnostic forms of 3 as well).
+ * Workspace contract: `work` is scratch, written before it is read (its previous contents
+ * never matter) and never past work_floats; pntf_tt_gemm_work_floats covers every panel and
+ * weight-gradient mode.  A smaller buffer never fails a panel or weight-gradient shape by
+ * itself: that path is skipped and the LDS-tiled kernel runs (a panel shape, K <= 256, never
+ * splits, so it needs no work at all).  Only when the LDS-tiled kernel splits K and `work` holds
+ * fewer than splits x M x N floats does the call return PNTF_ERR_WORKSPACE, before any launch
+ * (C untouched). */
 size_t pntf_tt_gemm_work_floats(int64_t M, int64_t N, int64_t K);
 int pntf_tt_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                  const float* B, int64_t ldb, float* C, int64_t ldc, float beta, float* work,

@@ -237,18 +237,20 @@ __device__ __forceinline__ f32x4 wbw_load(const float* p) {
 // Where a lane reads its environment's B rows: global memory (any table), or the table staged
 // in LDS once per workgroup when it fits (WBL_FLOATS; pntf_capi.hip picks the kernel).  The LDS
 // reads take the Fourier projections' and the fold's B loads off the in-order vmcnt queue.
+// Every use is of fl(2π·B) (load2pi): the staged table holds that product (the kernel scales
+// it once per workgroup while staging), the global-table reads multiply per use.
 template <bool BL>
 struct WBt {
-  __device__ __forceinline__ f32x4 load(const PairIO& io, int i) const {
-    return wbw_load(io.Bw + i);
+  __device__ __forceinline__ f32x4 load2pi(const PairIO& io, int i) const {
+    return TWO_PI * wbw_load(io.Bw + i);
   }
 };
 template <>
 struct WBt<true> {
-  const wlds_f* t;   // this lane's environment in the staged table
-  __device__ __forceinline__ f32x4 load(const PairIO&, int i) const {
+  const wlds_f* t;   // this lane's environment in the staged table of 2π·B
+  __device__ __forceinline__ f32x4 load2pi(const PairIO&, int i) const {
 #ifdef PNTF_ABL_NOBW
-    return wbw_load(reinterpret_cast<const float*>(static_cast<uintptr_t>(i)));
+    return TWO_PI * wbw_load(reinterpret_cast<const float*>(static_cast<uintptr_t>(i)));
 #else
     return *reinterpret_cast<const wlds_f4*>(t + i);
 #endif
@@ -281,11 +283,11 @@ __device__ __forceinline__ void wfourier_q(const PairIO& io, const BT& bt, int k
   for (int d = 0; d < DIM; ++d)
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      f32x4 b = bt.load(io, d * H + 32 * kt + 8 * u + 4 * h);
+      const f32x4 b = bt.load2pi(io, d * H + 32 * kt + 8 * u + 4 * h);
 #pragma unroll
       for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) q[c][4 * u + s] = fmaf(io.x[c][d], TWO_PI * b[s], q[c][4 * u + s]);
+        for (int s = 0; s < 4; ++s) q[c][4 * u + s] = fmaf(io.x[c][d], b[s], q[c][4 * u + s]);
     }
 }
 
@@ -328,7 +330,7 @@ __device__ __forceinline__ void wide_fold(Ring& ring, Rsrc W, const PairIO& io, 
           for (int u = 0; u < 4; ++u) {
             f32x4 bw[DIM];
 #pragma unroll
-            for (int d = 0; d < DIM; ++d) bw[d] = TWO_PI * bt.load(io, d * H + 32 * o + 8 * u + 4 * h);
+            for (int d = 0; d < DIM; ++d) bw[d] = bt.load2pi(io, d * H + 32 * o + 8 * u + 4 * h);
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -363,70 +365,58 @@ __device__ __forceinline__ void wide_fold(Ring& ring, Rsrc W, const PairIO& io, 
 //     needed beside the two banks and each input tile is split once per layer, shared by all
 //     its out tiles — the split is the largest VALU item (3.3 ms of 15.3 without sharing);
 //   * steps (kt, ot), ot fastest; input tile kt is split at ot = 0;
-//   * the epilogue runs in CHUNKS (4 registers of one out tile and column: the softplus/σ of 4
-//     elements and their 16-byte σ store, or the reverse sweep's σ multiply with its 16-byte
-//     σ load issued PDS steps ahead), CPS chunks per step from the step after the first out
-//     tile is final; the chunks that do not fit in the layer's last steps run in the first
-//     steps of the NEXT layer (its pre hook, XPend), each before that layer splits the tile.
-// Chunk j (tile t = j / (4 NC), column c = (j / 4) % NC, part q = j % 4) runs at step
-// E(j) = STEPS - OT + 1 + j / CPS of the layer (>= STEPS: the next layer's step E - STEPS).
-template <class L>
-struct XSched {
-  static constexpr int STEPS = L::OT * L::KT;
-  static constexpr int E(int j) { return STEPS - L::OT + 1 + j / L::CPS; }
-  static constexpr int P(int j) { return E(j) - L::PDS; }   // its σ prefetch (reverse)
+//   * the epilogue of out tile t (softplus/σ with its four 16-byte σ stores, or the reverse
+//     sweep's σ multiply) runs FUSED with the split of that tile in the NEXT layer, at its step
+//     (kt = t, ot = 0): the tile-column is read out of the bank once, the epilogue applied in
+//     VGPRs and the result split from there.  It is written back to the bank only where it is
+//     read again after that layer (KEEP: a residual C-init, the Fourier fold's second pass);
+//     the first layer of a residual block, whose output is nothing but the next layer's input,
+//     never returns to the bank.  Running the epilogue ahead of the split (in chunks over the
+//     steps before it) cost a bank read and write per element on top of the split's own read;
+//     VALU work costs the same wherever it is placed, so only the count matters;
+//   * the reverse sweep's σ tile of out tile t (4 NC quads) is loaded XPDS = 3 steps before
+//     the split that uses it: tile 0's in the layer's own step STEPS - 3, tile t's in the next
+//     layer's step t·OT - 3, after tile t - 1's quads were used at step (t - 1)·OT.
+constexpr int XPDS = 3;
+// no epilogue pending on the input bank: the tiles are split as they stand
+struct XPlain {
+  static constexpr bool EPI = false, PF = false;
+  __device__ __forceinline__ void prefetch(int) {}
 };
-// the chunks (and prefetches) of layer ly due at its step S (S >= STEPS: in the next layer)
-template <class L, int S>
-__device__ __forceinline__ void xdue(L& ly) {
-  if constexpr (L::NCH > 0) {
-    static_for<0, L::NCH>([&](auto jj) {
-      constexpr int j = decltype(jj)::value;
-      if constexpr (L::PF && XSched<L>::P(j) == S) ly.prefetch(j);
-    });
-    static_for<0, L::NCH>([&](auto jj) {
-      constexpr int j = decltype(jj)::value;
-      if constexpr (XSched<L>::E(j) == S) ly.chunk(j);
-    });
-  }
-}
-// the previous layer's pending chunks as the next layer's pre hook
-template <class L>
-struct XPend {
-  L& ly;
-  template <class ST>
-  __device__ __forceinline__ void operator()(ST) const {
-    xdue<L, XSched<L>::STEPS + ST::value>(ly);
-  }
-};
-// ... or all at once (before a phase that reads the whole bank): the remaining virtual steps
-// in order, so that the σ prefetch ring never holds more than its NSLOT quads (issuing every
-// pending prefetch first overwrote slots before their chunks read them)
+// every pending epilogue at once, written back (before a phase that reads the whole bank)
 template <class L>
 __device__ __forceinline__ void xflush(L& ly) {
-  if constexpr (L::NCH > 0) {
-    constexpr int S0 = XSched<L>::STEPS, S1 = XSched<L>::E(L::NCH - 1) + 1;
-    if constexpr (S1 > S0)
-      static_for<S0, S1>([&](auto ss) { xdue<L, decltype(ss)::value>(ly); });
+  if constexpr (L::EPI) {
+    static_for<0, L::OT>([&](auto tt) {
+      constexpr int t = decltype(tt)::value;
+      if constexpr (L::PF && t > 0) ly.prefetch(t);
+#pragma unroll
+      for (int c = 0; c < L::NC; ++c) ly.template tile<true>(t, c);
+    });
   }
 }
 
 // Banks in the AGPR file: the banks pass an empty asm with an AGPR operand in every step (the
-// VGPR file then holds the ring, the splits and the epilogue's temporaries; the chunks and
-// splits read a bank through v_accvgpr_read).  Left to the compiler both banks sit in the VGPR
-// file and 190-310 VGPRs spill; one bank in each file is spill-free only with a shorter ring
-// and ran 12-57 % slower (profiles/r06_wide_variants.txt r06o).
+// VGPR file then holds the ring, the splits and the epilogue's temporaries; the fused
+// epilogue + split reads a bank through v_accvgpr_read).  Left to the compiler both banks sit
+// in the VGPR file and 190-310 VGPRs spill; one bank in each file is spill-free only with a
+// shorter ring and ran 12-57 % slower (profiles/r06_wide_variants.txt
+// r06o).
 __device__ __forceinline__ void xagpr(f32x16& t) { asm("" : "+a"(t)); }
 
 // One Linear layer on split-bf16 MFMA, accumulating in ly.out (bank index c·OT + ot), input
 // bank `in` (c·KT + kt).  ly.init(ot) starts out tile ot at kt = 0 (bias MFMA / residual /
-// zero); ly's chunks run as above; pre(st) runs first in every step (the previous layer's
-// pending chunks, loads for the next layer).
-template <int OT, int KT, int NC, int SITE, class L, class PreF, class NextF>
+// zero).  pv is the layer that wrote `in` (pv.out is `in`) with its epilogue still pending, or
+// XPlain: step (kt, 0) takes input tile kt through pv's epilogue and splits the result; KEEP
+// says whether the bank gets it back.  pre(st) runs first in every step (loads for the next
+// layer).
+template <int OT, int KT, int NC, int SITE, bool KEEP, class L, class P, class PreF, class NextF>
 __device__ __forceinline__ void xlayer(Ring& ring, Rsrc W, int wbase, f32x16 (&in)[8],
-                                       int lane, L& ly, PreF pre, NextF naddr) {
+                                       int lane, L& ly, P& pv, PreF pre, NextF naddr) {
   static_assert(NC * KT <= 8 && NC * OT <= 8, "bank size");
   static_assert(L::OT == OT && L::KT == KT && L::NC == NC, "layer object shape");
+  static_assert(XPDS < OT, "tile t - 1's sigma quads are used before tile t's are loaded");
+  if constexpr (P::EPI) static_assert(P::OT == KT && P::NC == NC, "previous layer's shape");
   constexpr int STEPS = OT * KT;
   wbf16x8 xs[NC][2][3];
   run_steps<STEPS, WNL, wnext_nl<NextF>(), SITE>(
@@ -434,11 +424,17 @@ __device__ __forceinline__ void xlayer(Ring& ring, Rsrc W, int wbase, f32x16 (&i
         constexpr int S = decltype(st)::value;
         constexpr int kt = S / OT, ot = S % OT;
         pre(st);
+        if constexpr (P::PF && (S + XPDS) % OT == 0 && (S + XPDS) / OT < KT)
+          pv.prefetch((S + XPDS) / OT);
         if constexpr (ot == 0) {
 #pragma unroll
-          for (int c = 0; c < NC; ++c)
+          for (int c = 0; c < NC; ++c) {
+            f32x16 v;
+            if constexpr (P::EPI) v = pv.template tile<KEEP>(kt, c);
+            else v = in[c * KT + kt];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) wx6_split(in[c * KT + kt], b, xs[c][b]);
+            for (int b = 0; b < 2; ++b) wx6_split(v, b, xs[c][b]);
+          }
         }
         if constexpr (kt == 0) ly.init(ot);
 #pragma unroll
@@ -454,17 +450,19 @@ __device__ __forceinline__ void xlayer(Ring& ring, Rsrc W, int wbase, f32x16 (&i
           xagpr(in[t]);
           xagpr(ly.out[t]);
         }
-        xdue<L, S>(ly);
+        if constexpr (L::PF && S == STEPS - XPDS) ly.prefetch(0);
       });
 }
 
-// ---- layer objects: OT, KT, NC; CPS chunks per step; NCH chunks; PF/PDS: σ prefetch
+// ---- layer objects: OT, KT, NC; EPI: an epilogue pends on the out tiles; PF: it needs σ
+// prefetches.  tile<KEEP>(t, c) reads out tile-column (t, c) from the bank, applies the
+// epilogue, writes the result back when KEEP, and returns it.
 // forward Linear + softplus10: out = sp(A·in + b (+ out if RES)); σ10 saved when SAVE (scratch
 // tile sc0 + c·OT + t, or LDS tiles when IN_LDS); ACT0: encoder[0]'s compat quirk (:435-438)
 template <int OT_, int KT_, int NC_, bool RES, bool SAVE, bool IN_LDS = false, bool ACT0 = false>
 struct XFwdAct {
-  static constexpr int OT = OT_, KT = KT_, NC = NC_, CPS = NC_, NCH = NC_ * OT_ * 4, PDS = 0;
-  static constexpr bool PF = false;
+  static constexpr int OT = OT_, KT = KT_, NC = NC_;
+  static constexpr bool EPI = true, PF = false;
   f32x16 (&out)[8];
   WScratch sc;
   int sc0, lane;
@@ -477,25 +475,31 @@ struct XFwdAct {
       out[c * OT + ot] = mfma32(bc(ot), 1.f, RES ? out[c * OT + ot] : zero16());
   }
   __device__ __forceinline__ void prefetch(int) {}
-  __device__ __forceinline__ void chunk(int j) {
-    const int t = j / (4 * NC), c = (j / 4) % NC, q = j % 4;
-    f32x4 g;
+  template <bool KEEP>
+  __device__ __forceinline__ f32x16 tile(int t, int c) {
+    f32x16 v = out[c * OT + t];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const SpSig v = wsp_sig(out[c * OT + t][4 * q + s]);
-      out[c * OT + t][4 * q + s] = v.sp;
-      g[s] = ACT0 ? fmaf(cm, __builtin_amdgcn_rcpf(2.f - v.sg) - v.sg, v.sg) : v.sg;
+    for (int q = 0; q < 4; ++q) {
+      f32x4 g;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const SpSig r = wsp_sig(v[4 * q + s]);
+        v[4 * q + s] = r.sp;
+        g[s] = ACT0 ? fmaf(cm, __builtin_amdgcn_rcpf(2.f - r.sg) - r.sg, r.sg) : r.sg;
+      }
+      if constexpr (SAVE && IN_LDS) wl.p[((sc0 + c * OT + t) * 4 + q) * 64] = g;
+      // nt: the σ stores stream past the L2 that holds the weights
+      else if constexpr (SAVE) bstore<AUX_NT>(sc.r, g, lane * 16, (sc0 + c * OT + t) * 4096 + q * 1024);
     }
-    if constexpr (SAVE && IN_LDS) wl.p[((sc0 + c * OT + t) * 4 + q) * 64] = g;
-    // nt: the σ stores stream past the L2 that holds the weights
-    else if constexpr (SAVE) bstore<AUX_NT>(sc.r, g, lane * 16, (sc0 + c * OT + t) * 4096 + q * 1024);
+    if constexpr (KEEP) out[c * OT + t] = v;
+    return v;
   }
 };
 // forward Linear without activation (encoder[-1], :234): nothing pending
 template <int OT_, int KT_, int NC_>
 struct XFwdLin {
-  static constexpr int OT = OT_, KT = KT_, NC = NC_, CPS = 1, NCH = 0, PDS = 0;
-  static constexpr bool PF = false;
+  static constexpr int OT = OT_, KT = KT_, NC = NC_;
+  static constexpr bool EPI = false, PF = false;
   f32x16 (&out)[8];
   BiasCols<OT_> bc;
   __device__ __forceinline__ void init(int ot) {
@@ -503,36 +507,46 @@ struct XFwdLin {
     for (int c = 0; c < NC; ++c) out[c * OT + ot] = mfma32(bc(ot), 1.f, zero16());
   }
   __device__ __forceinline__ void prefetch(int) {}
-  __device__ __forceinline__ void chunk(int) {}
 };
-// reverse: out = (A^T·in (+ out if RES)) ⊙ σ tile mul0 + c·OT + t (if MUL); each chunk's σ part
-// is loaded PDS = 3 steps ahead into a ring of NSLOT register quads
+// reverse: out = (A^T·in (+ out if RES)) ⊙ σ tile mul0 + c·OT + t (if MUL); a tile's σ quads
+// (4 per column) are loaded XPDS steps ahead of the fused split that multiplies by them
 template <int OT_, int KT_, int NC_, bool RES, bool MUL>
 struct XBwd {
-  static constexpr int OT = OT_, KT = KT_, NC = NC_, CPS = NC_, NCH = MUL ? NC_ * OT_ * 4 : 0;
-  static constexpr int PDS = 3, NSLOT = CPS * (PDS + 1);
-  static constexpr bool PF = MUL;
+  static constexpr int OT = OT_, KT = KT_, NC = NC_;
+  static constexpr bool EPI = MUL, PF = MUL;
   f32x16 (&out)[8];
   WScratch sc;
   int mul0, lane;
-  f32x4 sg[NSLOT];
+  f32x4 sg[4 * NC_];
   __device__ __forceinline__ void init(int ot) {
     if constexpr (!RES) {
 #pragma unroll
       for (int c = 0; c < NC; ++c) out[c * OT + ot] = zero16();
     }
   }
-  __device__ __forceinline__ void prefetch(int j) {
-    const int t = j / (4 * NC), c = (j / 4) % NC, q = j % 4;
-    sg[j % NSLOT] = __builtin_bit_cast(
-        f32x4, __builtin_amdgcn_raw_buffer_load_b128(sc.r, lane * 16,
-                                                     (mul0 + c * OT + t) * 4096 + q * 1024,
-                                                     AUX_LOAD));
-  }
-  __device__ __forceinline__ void chunk(int j) {
-    const int t = j / (4 * NC), c = (j / 4) % NC, q = j % 4;
+  __device__ __forceinline__ void prefetch(int t) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) out[c * OT + t][4 * q + s] *= sg[j % NSLOT][s];
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        sg[c * 4 + q] = __builtin_bit_cast(
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(sc.r, lane * 16,
+                                                         (mul0 + c * OT + t) * 4096 + q * 1024,
+                                                         AUX_LOAD));
+  }
+  template <bool KEEP>
+  __device__ __forceinline__ f32x16 tile(int t, int c) {
+    // the product is rounded to fp32 before the split subtracts its leading term from it: it
+    // must not contract into that subtraction as an fma (the bank gets the rounded product,
+    // and the three terms must sum to it)
+#pragma clang fp contract(off)
+    f32x16 v = out[c * OT + t];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) v[4 * q + s] *= sg[c * 4 + q][s];
+    if constexpr (KEEP) out[c * OT + t] = v;
+    return v;
   }
 };
 
@@ -546,10 +560,13 @@ constexpr bool xfold() { return std::is_same<BT, WBt<true>>::value; }
 // pass p the four out tiles sin(o), cos(o) for o = 2p, 2p + 1 accumulate in X (dead here:
 // X[c·4 + ot_local]) over the 4 input tiles of Y, each input tile split once per pass and
 // shared by the 4 tiles; after the pass the two feature tiles fold into dτ/dx_c as wide_fold.
-template <int DIM, class BT, class AfterF>
+// pv is encoder block 0's first layer transposed (a0ᵀ, out = Y) with its σ multiply pending:
+// pass 0's split of tile kt runs it (as xlayer does) and writes Y back for pass 1.
+template <int DIM, class BT, class P, class AfterF>
 __device__ __forceinline__ void wide_fold_x(Ring& ring, Rsrc W, const PairIO& io, BT bt,
-                                            f32x16 (&X)[8], f32x16 (&Y)[8], int lane,
+                                            f32x16 (&X)[8], f32x16 (&Y)[8], P& pv, int lane,
                                             float (&ds)[DIM], float (&dg)[DIM], AfterF after) {
+  static_assert(P::OT == 4 && P::NC == 2, "previous layer's shape");
   const int h = lane >> 5;
   float acc[2][DIM];
 #pragma unroll
@@ -559,11 +576,17 @@ __device__ __forceinline__ void wide_fold_x(Ring& ring, Rsrc W, const PairIO& io
       ring, W, lane * 16, WFoldXHead{}, after, [&](auto st, const f32x4 (&a)[WNL]) {
         constexpr int S = decltype(st)::value;
         constexpr int p = S / 16, kt = (S / 4) % 4, otl = S % 4;
+        if constexpr (P::PF && p == 0 && (S + XPDS) % 4 == 0 && (S + XPDS) / 4 < 4)
+          pv.prefetch((S + XPDS) / 4);
         if constexpr (otl == 0) {
 #pragma unroll
-          for (int c = 0; c < 2; ++c)
+          for (int c = 0; c < 2; ++c) {
+            f32x16 v;
+            if constexpr (P::EPI && p == 0) v = pv.template tile<true>(kt, c);
+            else v = Y[c * 4 + kt];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) wx6_split(Y[c * 4 + kt], b, xs[c][b]);
+            for (int b = 0; b < 2; ++b) wx6_split(v, b, xs[c][b]);
+          }
         }
         if constexpr (kt == 0) {
 #pragma unroll
@@ -588,7 +611,7 @@ __device__ __forceinline__ void wide_fold_x(Ring& ring, Rsrc W, const PairIO& io
               f32x4 bw[DIM];
 #pragma unroll
               for (int d = 0; d < DIM; ++d)
-                bw[d] = TWO_PI * bt.load(io, d * H + 32 * o + 8 * u + 4 * h);
+                bw[d] = bt.load2pi(io, d * H + 32 * o + 8 * u + 4 * h);
 #pragma unroll
               for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -617,7 +640,9 @@ __device__ __forceinline__ void wide_fold_x(Ring& ring, Rsrc W, const PairIO& io
 // ---------------------------------------------------------------- forward pass
 // NN.out on 32 pairs.  GRAD: save σ tiles.  On entry the ring holds WE0Head; on return the
 // first PF steps of `after`.  Returns τ of the lane's pair (same in both lane halves).  The
-// encoder[0] epilogue and every layer's run as chunks (above).
+// encoder[0] epilogue and every layer's run fused with the next layer's split (above); KEEP
+// where the tile is a residual (e0, b0, gb), not where it is only the next layer's input (a0,
+// a1, b1, ga, the last gb).
 template <int DIM, bool GRAD, class BT, class AfterF>
 __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO& io, BT bt,
                                                 f32x16 (&X)[8], f32x16 (&Y)[8], WScratch sc,
@@ -673,7 +698,6 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
           // next sin/cos tile's projections, after this tile's MFMAs are issued
           if constexpr (ot == 3 && kt < 3) wfourier_q<DIM>(io, bt, kt + 1, h, q);
           if constexpr (S == 16) a0.bc.load(W, lane, B_EBLK);
-          xdue<decltype(e0), S>(e0);
         });
   }
 
@@ -685,25 +709,21 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
     XFwdAct<4, 4, 2, false, GRAD> a1{Y, sc, WT_EBLK + 16, lane, {}, wl, 0.f};
     XFwdAct<4, 4, 2, true, GRAD> b1{X, sc, WT_EBLK + 24, lane, {}, wl, 0.f};
     XFwdLin<4, 4, 2> e3{Y, {}};
-    xlayer<4, 4, 2, SITE_FWD_ENC>(ring, W, WE, X, lane, a0,
-                                  both(XPend<decltype(e0)>{e0},
-                                       at<0>([&] { b0.bc.load(W, lane, B_EBLK + 128); })),
-                                  WHead{WE + SZ_E * 4});
-    xlayer<4, 4, 2, SITE_FWD_ENC>(ring, W, WE + SZ_E * 4, Y, lane, b0,
-                                  both(XPend<decltype(a0)>{a0},
-                                       at<0>([&] { a1.bc.load(W, lane, B_EBLK + 256); })),
-                                  WHead{WE + 2 * SZ_E * 4});
-    xlayer<4, 4, 2, SITE_FWD_ENC>(ring, W, WE + 2 * SZ_E * 4, X, lane, a1,
-                                  both(XPend<decltype(b0)>{b0},
-                                       at<0>([&] { b1.bc.load(W, lane, B_EBLK + 384); })),
-                                  WHead{WE + 3 * SZ_E * 4});
-    xlayer<4, 4, 2, SITE_FWD_ENC>(ring, W, WE + 3 * SZ_E * 4, Y, lane, b1,
-                                  both(XPend<decltype(a1)>{a1},
-                                       at<0>([&] { e3.bc.load(W, lane, B_E3); })),
-                                  WHead{WF + OFF_E3 * 4});
+    xlayer<4, 4, 2, SITE_FWD_ENC, true>(ring, W, WE, X, lane, a0, e0,
+                                        at<0>([&] { b0.bc.load(W, lane, B_EBLK + 128); }),
+                                        WHead{WE + SZ_E * 4});
+    xlayer<4, 4, 2, SITE_FWD_ENC, false>(ring, W, WE + SZ_E * 4, Y, lane, b0, a0,
+                                         at<0>([&] { a1.bc.load(W, lane, B_EBLK + 256); }),
+                                         WHead{WE + 2 * SZ_E * 4});
+    xlayer<4, 4, 2, SITE_FWD_ENC, true>(ring, W, WE + 2 * SZ_E * 4, X, lane, a1, b0,
+                                        at<0>([&] { b1.bc.load(W, lane, B_EBLK + 384); }),
+                                        WHead{WE + 3 * SZ_E * 4});
+    xlayer<4, 4, 2, SITE_FWD_ENC, false>(ring, W, WE + 3 * SZ_E * 4, Y, lane, b1, a1,
+                                         at<0>([&] { e3.bc.load(W, lane, B_E3); }),
+                                         WHead{WF + OFF_E3 * 4});
     // ---- encoder[-1] (:234) -> Y (zs = Y[0..3], zg = Y[4..7])
-    xlayer<4, 4, 2, SITE_FWD_ENC>(ring, W, WF + OFF_E3 * 4, X, lane, e3, XPend<decltype(b1)>{b1},
-                                  WHead{WF + OFF_GBLK * 4});
+    xlayer<4, 4, 2, SITE_FWD_ENC, false>(ring, W, WF + OFF_E3 * 4, X, lane, e3, b1, NoPre{},
+                                         WHead{WF + OFF_GBLK * 4});
   }
 
   // ---- symmetric smooth max / min merge (:236-244) -> X (u = [M | m], 8 tiles)
@@ -725,13 +745,14 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
   }
 
   // ---- generator residual blocks (:246-249), rotated so that one loop body carries a
-  // layer's pending chunks into the next: ga0; (gb_i, ga_{i+1}) for i = 0, 1; gb2; g3
+  // layer's pending epilogue into the next: ga0; (gb_i, ga_{i+1}) for i = 0, 1; gb2; g3
   XFwdAct<8, 8, 1, false, GRAD> ga{Y, sc, WT_GBLK, lane, {}, wl, 0.f};
   XFwdAct<8, 8, 1, true, GRAD> gb{X, sc, WT_GBLK + 8, lane, {}, wl, 0.f};
   ga.bc.load(W, lane, B_GBLK);
-  xlayer<8, 8, 1, SITE_FWD_GEN>(ring, W, WF + OFF_GBLK * 4, X, lane, ga,
-                                at<0>([&] { gb.bc.load(W, lane, B_GBLK + 256); }),
-                                WHead{WF + (OFF_GBLK + SZ_G) * 4});
+  XPlain plain;
+  xlayer<8, 8, 1, SITE_FWD_GEN, true>(ring, W, WF + OFF_GBLK * 4, X, lane, ga, plain,
+                                      at<0>([&] { gb.bc.load(W, lane, B_GBLK + 256); }),
+                                      WHead{WF + (OFF_GBLK + SZ_G) * 4});
 #pragma unroll 1
   for (int i = 0; i < 2; ++i) {
     const int wb = opaque(WF + (OFF_GBLK + (2 * i + 1) * SZ_G) * 4);
@@ -739,25 +760,20 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
     const int wn = opaque(WF + (OFF_GBLK + (2 * i + 3) * SZ_G) * 4);
     const int ba = opaque(B_GBLK + (2 * i + 2) * 256);
     gb.sc0 = opaque(WT_GBLK + 16 * i + 8);
-    xlayer<8, 8, 1, SITE_FWD_GEN>(ring, W, wb, Y, lane, gb,
-                                  both(XPend<decltype(ga)>{ga},
-                                       at<0>([&] { ga.bc.load(W, lane, ba); })),
-                                  WHead{wa});
+    xlayer<8, 8, 1, SITE_FWD_GEN, false>(ring, W, wb, Y, lane, gb, ga,
+                                         at<0>([&] { ga.bc.load(W, lane, ba); }), WHead{wa});
     ga.sc0 = opaque(WT_GBLK + 16 * i + 16);
-    xlayer<8, 8, 1, SITE_FWD_GEN>(ring, W, wa, X, lane, ga,
-                                  both(XPend<decltype(gb)>{gb},
-                                       at<0>([&] { gb.bc.load(W, lane, ba + 256); })),
-                                  WHead{wn});
+    xlayer<8, 8, 1, SITE_FWD_GEN, true>(ring, W, wa, X, lane, ga, gb,
+                                        at<0>([&] { gb.bc.load(W, lane, ba + 256); }),
+                                        WHead{wn});
   }
   // ---- generator block 2's second layer, then generator[-2] + act (:251-252) -> Y[0..3]
   XFwdAct<4, 8, 1, false, GRAD, true> g3{Y, sc, WL_G3, lane, {}, wl, 0.f};
   gb.sc0 = WT_GBLK + 16 * 2 + 8;
-  xlayer<8, 8, 1, SITE_FWD_GEN>(ring, W, WF + (OFF_GBLK + 5 * SZ_G) * 4, Y, lane, gb,
-                                both(XPend<decltype(ga)>{ga},
-                                     at<0>([&] { g3.bc.load(W, lane, B_G3); })),
-                                WHead{WF + OFF_G3 * 4});
-  xlayer<4, 8, 1, SITE_FWD_GEN>(ring, W, WF + OFF_G3 * 4, X, lane, g3, XPend<decltype(gb)>{gb},
-                                after);
+  xlayer<8, 8, 1, SITE_FWD_GEN, false>(ring, W, WF + (OFF_GBLK + 5 * SZ_G) * 4, Y, lane, gb, ga,
+                                       at<0>([&] { g3.bc.load(W, lane, B_G3); }),
+                                       WHead{WF + OFF_G3 * 4});
+  xlayer<4, 8, 1, SITE_FWD_GEN, false>(ring, W, WF + OFF_G3 * 4, X, lane, g3, gb, NoPre{}, after);
   xflush(g3);
   // ---- head generator[-1] + sigmoid(0.1 y) (:254-255)
   float part = 0.f;
@@ -799,14 +815,16 @@ __device__ __forceinline__ void wide_backward_x(Ring& ring, Rsrc W, const PairIO
   }
   // du = G3^T dv ⊙ σ10(y2 of generator block 2) -> X   (G3^T: 256 x 128, OT 8, KT 4)
   XBwd<8, 4, 1, false, true> l3{X, sc, WT_GBLK + 16 * 2 + 8, lane, {}};
-  xlayer<8, 4, 1, SITE_BWD_GEN>(ring, W, WB + OFF_G3 * 4, Y, lane, l3, NoPre{},
-                                WHead{WB + (OFF_GBLK + 5 * SZ_G) * 4});
+  XPlain plain;
+  xlayer<8, 4, 1, SITE_BWD_GEN, true>(ring, W, WB + OFF_G3 * 4, Y, lane, l3, plain, NoPre{},
+                                      WHead{WB + (OFF_GBLK + 5 * SZ_G) * 4});
   // ---- generator blocks, reverse (:615-618), rotated: lb_2; (la_i, lb_{i-1}) for i = 2, 1;
-  // la_0 (no σ: it hands over to encoder[-1]^T)
+  // la_0 (no σ: it hands over to encoder[-1]^T).  l3's and la's products stay in the bank as
+  // the next la's residual (KEEP); lb's feed only the next transpose.
   XBwd<8, 8, 1, false, true> lb{Y, sc, WT_GBLK + 16 * 2, lane, {}};
   XBwd<8, 8, 1, true, true> la{X, sc, 0, lane, {}};
-  xlayer<8, 8, 1, SITE_BWD_GEN>(ring, W, WB + (OFF_GBLK + 5 * SZ_G) * 4, X, lane, lb,
-                                XPend<decltype(l3)>{l3}, WHead{WB + (OFF_GBLK + 4 * SZ_G) * 4});
+  xlayer<8, 8, 1, SITE_BWD_GEN, true>(ring, W, WB + (OFF_GBLK + 5 * SZ_G) * 4, X, lane, lb, l3,
+                                      NoPre{}, WHead{WB + (OFF_GBLK + 4 * SZ_G) * 4});
 #pragma unroll 1
   for (int i = 2; i >= 1; --i) {
     const int wa = opaque(WB + (OFF_GBLK + (2 * i) * SZ_G) * 4);
@@ -814,15 +832,15 @@ __device__ __forceinline__ void wide_backward_x(Ring& ring, Rsrc W, const PairIO
     const int wn = opaque(WB + (OFF_GBLK + (2 * i - 2) * SZ_G) * 4);
     // du = G_i^T da + dr, then ⊙ σ10(y2_{i-1})
     la.mul0 = opaque(WT_GBLK + 16 * (i - 1) + 8);
-    xlayer<8, 8, 1, SITE_BWD_GEN>(ring, W, wa, Y, lane, la, XPend<decltype(lb)>{lb}, WHead{wb});
+    xlayer<8, 8, 1, SITE_BWD_GEN, false>(ring, W, wa, Y, lane, la, lb, NoPre{}, WHead{wb});
     // da = (G1_{i-1}^T dr) ⊙ σ10(y1_{i-1}) -> Y
     lb.mul0 = opaque(WT_GBLK + 16 * (i - 1));
-    xlayer<8, 8, 1, SITE_BWD_GEN>(ring, W, wb, X, lane, lb, XPend<decltype(la)>{la}, WHead{wn});
+    xlayer<8, 8, 1, SITE_BWD_GEN, true>(ring, W, wb, X, lane, lb, la, NoPre{}, WHead{wn});
   }
   {
     XBwd<8, 8, 1, true, false> l0{X, sc, 0, lane, {}};
-    xlayer<8, 8, 1, SITE_BWD_GEN>(ring, W, WB + OFF_GBLK * 4, Y, lane, l0,
-                                  XPend<decltype(lb)>{lb}, WHead{WB + OFF_E3 * 4});
+    xlayer<8, 8, 1, SITE_BWD_GEN, false>(ring, W, WB + OFF_GBLK * 4, Y, lane, l0, lb, NoPre{},
+                                         WHead{WB + OFF_E3 * 4});
   }
   // ---- merge Jacobian (:620-627): X[0..3] = dzs, X[4..7] = dzg
 #pragma unroll
@@ -841,24 +859,25 @@ __device__ __forceinline__ void wide_backward_x(Ring& ring, Rsrc W, const PairIO
     XBwd<4, 4, 2, true, true> a1{Y, sc, WT_EBLK + 8, lane, {}};
     XBwd<4, 4, 2, false, true> b0{X, sc, WT_EBLK, lane, {}};
     XBwd<4, 4, 2, true, true> a0{Y, sc, WT_E0, lane, {}};
-    xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WB + OFF_E3 * 4, X, lane, e3, NoPre{},
-                                  WHead{WE + 3 * SZ_E * 4});
-    xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WE + 3 * SZ_E * 4, Y, lane, b1, XPend<decltype(e3)>{e3},
-                                  WHead{WE + 2 * SZ_E * 4});
-    xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WE + 2 * SZ_E * 4, X, lane, a1, XPend<decltype(b1)>{b1},
-                                  WHead{WE + 1 * SZ_E * 4});
-    xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WE + 1 * SZ_E * 4, Y, lane, b0, XPend<decltype(a1)>{a1},
-                                  WHead{WE});
-    if constexpr (xfold<BT>())
-      xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WE, X, lane, a0, XPend<decltype(b0)>{b0},
-                                    WFoldXHead{});
-    else
-      xlayer<4, 4, 2, SITE_BWD_ENC>(ring, W, WE, X, lane, a0, XPend<decltype(b0)>{b0},
-                                    WFoldHead{});
-    xflush(a0);
+    xlayer<4, 4, 2, SITE_BWD_ENC, true>(ring, W, WB + OFF_E3 * 4, X, lane, e3, plain, NoPre{},
+                                        WHead{WE + 3 * SZ_E * 4});
+    xlayer<4, 4, 2, SITE_BWD_ENC, true>(ring, W, WE + 3 * SZ_E * 4, Y, lane, b1, e3, NoPre{},
+                                        WHead{WE + 2 * SZ_E * 4});
+    xlayer<4, 4, 2, SITE_BWD_ENC, false>(ring, W, WE + 2 * SZ_E * 4, X, lane, a1, b1, NoPre{},
+                                         WHead{WE + 1 * SZ_E * 4});
+    xlayer<4, 4, 2, SITE_BWD_ENC, true>(ring, W, WE + 1 * SZ_E * 4, Y, lane, b0, a1, NoPre{},
+                                        WHead{WE});
+    // a0ᵀ's σ multiply runs in the split-bf16 fold's first-pass splits; the fp32 fold reads
+    // all of Y in every step, so there it runs first
+    if constexpr (xfold<BT>()) {
+      xlayer<4, 4, 2, SITE_BWD_ENC, false>(ring, W, WE, X, lane, a0, b0, NoPre{}, WFoldXHead{});
+      wide_fold_x<DIM>(ring, W, io, bt, X, Y, a0, lane, ds, dg, after);
+    } else {
+      xlayer<4, 4, 2, SITE_BWD_ENC, false>(ring, W, WE, X, lane, a0, b0, NoPre{}, WFoldHead{});
+      xflush(a0);
+      wide_fold<DIM>(ring, W, io, bt, Y, lane, ds, dg, after);
+    }
   }
-  if constexpr (xfold<BT>()) wide_fold_x<DIM>(ring, W, io, bt, X, Y, lane, ds, dg, after);
-  else wide_fold<DIM>(ring, W, io, bt, Y, lane, ds, dg, after);
 }
 
 // ---------------------------------------------------------------- kernel
@@ -885,11 +904,11 @@ __global__ __launch_bounds__(256, 1) void wide_field_kernel(FieldArgs a) {
                 (const wlds_f*)(whead + wv * (H / 4))};
   ((wlds_f*)(whead + wv * (H / 4)))[lane] = a.P[OFF_BIAS + B_G4W + lane];
   ((wlds_f*)(whead + wv * (H / 4)))[lane + 64] = a.P[OFF_BIAS + B_G4W + lane + 64];
-  __shared__ f32x4 wbtab[BL ? WBL_FLOATS / 4 : 1];
+  __shared__ f32x4 wbtab[BL ? WBL_FLOATS / 4 : 1];   // 2π·B (WBt<true>)
   if constexpr (BL) {   // the host checked n_env · DIM · H <= WBL_FLOATS
     const int nb4 = a.n_env * (DIM * H / 4);
     for (int i = threadIdx.x; i < nb4; i += 256)
-      wbtab[i] = *reinterpret_cast<const f32x4*>(a.Btab + 4 * i);
+      wbtab[i] = TWO_PI * *reinterpret_cast<const f32x4*>(a.Btab + 4 * i);
   }
   Ring ring;
   ring_fill<WNL>(ring, W, lane * 16, WE0Head{});

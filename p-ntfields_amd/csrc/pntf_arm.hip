@@ -45,20 +45,6 @@ struct ArmChain {
   int dof;
 };
 
-int fail(const char* what) {
-  snprintf(error_buffer(), ERROR_BYTES, "%s", what);
-  return PNTF_ERR_ARG;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(error_buffer(), ERROR_BYTES, "%s: %s", what, hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
-}
-
 // C (3x4) = A (3x4) · B (3x4), both with an implied last row (0 0 0 1)
 __device__ __forceinline__ void mul34(const float* A, const float* B, float* C) {
 #pragma unroll
@@ -187,17 +173,6 @@ __global__ __launch_bounds__(BLOCK) void arm_mesh_distance_kernel(
   }
 }
 
-__global__ void arm_fill_kernel(unsigned int* __restrict__ acc, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] = 0x7f800000u;
-}
-
-__global__ void arm_finalize_kernel(float* __restrict__ dist, int64_t n, float cap) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    dist[i] = fminf(sqrtf(__uint_as_float(reinterpret_cast<unsigned int*>(dist)[i])), cap);
-}
-
 }  // namespace
 
 extern "C" {
@@ -245,11 +220,12 @@ int pntf_arm_mesh_distance(const float* theta, int64_t n, int dof, int frames,
   if (n > 0x7fffffff) return fail("pntf_arm_mesh_distance: too many configurations");
   unsigned int* acc = reinterpret_cast<unsigned int*>(dist);
   const unsigned g1 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(arm_fill_kernel, dim3(g1), dim3(256), 0, stream, acc, n);
+  hipLaunchKernelGGL((fill_kernel<unsigned int, D2_INF>), dim3(g1), dim3(256), 0, stream, acc,
+                     n);
   if (chunks > 0)
     hipLaunchKernelGGL(arm_mesh_distance_kernel, dim3((unsigned)n, (unsigned)chunks),
                        dim3(BLOCK), 0, stream, theta, ch, verts, tris, t, cap * cap, acc);
-  hipLaunchKernelGGL(arm_finalize_kernel, dim3(g1), dim3(256), 0, stream, dist, n, cap);
+  hipLaunchKernelGGL(finalize_kernel, dim3(g1), dim3(256), 0, stream, dist, n, cap);
   return check_launch("arm_mesh_distance_kernel");
 }
 

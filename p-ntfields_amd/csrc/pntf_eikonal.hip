@@ -29,27 +29,13 @@
 
 namespace {
 
-using pntf_mesh::error_buffer;
-using pntf_mesh::ERROR_BYTES;
+using pntf_mesh::check_launch;
+using pntf_mesh::fail;
 
 constexpr int TILE = 8;                      // nodes per tile edge
 constexpr int HALO = TILE + 2;               // LDS edge: the tile and one node on either side
 constexpr int TILE_LANES = TILE * TILE * TILE;
 constexpr int LDS_NODES = HALO * HALO * HALO;
-
-int fail(const char* what) {
-  snprintf(error_buffer(), ERROR_BYTES, "%s", what);
-  return PNTF_ERR_ARG;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(error_buffer(), ERROR_BYTES, "%s: %s", what, hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
-}
 
 // the tile's origin from the flat tile index (k fastest, as the nodes)
 __device__ __forceinline__ void tile_origin(int32_t n, int& i0, int& j0, int& k0) {

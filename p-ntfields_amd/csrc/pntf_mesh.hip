@@ -30,8 +30,23 @@
 #include "pntf_mesh_geom.h"
 
 namespace pntf_mesh {
-thread_local char g_err[ERROR_BYTES] = "";
-char* error_buffer() { return g_err; }
+
+thread_local char g_err[512] = "";   // the text behind pntf_mesh_last_error
+
+int fail(const char* what) {
+  snprintf(g_err, sizeof g_err, "%s", what);
+  return PNTF_ERR_ARG;
+}
+
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
+    return PNTF_ERR_HIP;
+  }
+  return PNTF_OK;
+}
+
 }  // namespace pntf_mesh
 
 namespace {
@@ -39,20 +54,6 @@ namespace {
 using namespace pntf_mesh;  // record, tri_d2, reductions, BLOCK / PTS / PPW (pntf_mesh_geom.h)
 
 constexpr int TARGET_WG = 2048;  // 8 workgroups per CU on 256 CUs
-
-int fail(const char* what) {
-  snprintf(g_err, ERROR_BYTES, "%s", what);
-  return PNTF_ERR_ARG;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, ERROR_BYTES, "%s: %s", what, hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
-}
 
 // grid (ceil(n/PPW), n_chunks); chunk y covers triangles [y*per, min(t,(y+1)*per)).  Each
 // lane owns PTS points (PPW = 256·PTS per workgroup), so one LDS record read serves PTS tests.
@@ -142,21 +143,11 @@ __global__ __launch_bounds__(BLOCK) void mesh_distance_kernel(
   }
 }
 
-__global__ void fill_inf_kernel(unsigned int* __restrict__ acc, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] = 0x7f800000u;
-}
-
-__global__ void finalize_kernel(float* __restrict__ dist, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dist[i] = sqrtf(__uint_as_float(reinterpret_cast<unsigned int*>(dist)[i]));
-}
-
 }  // namespace
 
 extern "C" {
 
-const char* pntf_mesh_last_error(void) { return g_err; }
+const char* pntf_mesh_last_error(void) { return pntf_mesh::g_err; }
 
 int pntf_mesh_chunks(int64_t n, int64_t t) {
   if (n <= 0 || t <= 0) return 1;
@@ -190,10 +181,11 @@ int pntf_point_mesh_distance(const float* pts, int64_t n, const float* tris, int
   }
   unsigned int* acc = reinterpret_cast<unsigned int*>(dist);
   const unsigned g1 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(fill_inf_kernel, dim3(g1), dim3(256), 0, stream, acc, n);
+  hipLaunchKernelGGL((fill_kernel<unsigned int, D2_INF>), dim3(g1), dim3(256), 0, stream, acc,
+                     n);
   hipLaunchKernelGGL(mesh_distance_kernel<true>, grid, dim3(BLOCK), 0, stream, pts, n, tris, t,
                      per, dist, acc);
-  hipLaunchKernelGGL(finalize_kernel, dim3(g1), dim3(256), 0, stream, dist, n);
+  hipLaunchKernelGGL(finalize_kernel, dim3(g1), dim3(256), 0, stream, dist, n, INFINITY);
   return check_launch("mesh_distance_kernel");
 }
 

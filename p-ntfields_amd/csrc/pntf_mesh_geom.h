@@ -1,7 +1,9 @@
 // Point -> triangle geometry shared by the mesh-distance kernels (pntf_mesh.hip: points given;
-// pntf_arm.hip: points posed by forward kinematics in the kernel): the per-triangle LDS record,
-// the branch-free squared distance and the wave reductions.  One definition, so both kernels
-// compute a (point, triangle) pair to the same bits.
+// pntf_arm.hip: points posed by forward kinematics in the kernel; pntf_path.hip: the points of
+// polylines): the per-triangle LDS record, the branch-free squared distance, the culling test
+// and the wave reductions.  One definition, so every kernel computes a (point, triangle) pair
+// to the same bits.  Also the fill and finalize passes that bracket a launch which combines
+// through an atomic min.
 #ifndef PNTF_MESH_GEOM_H_
 #define PNTF_MESH_GEOM_H_
 
@@ -10,9 +12,11 @@
 
 namespace pntf_mesh {
 
-// thread-local error text behind pntf_mesh_last_error (defined in pntf_mesh.hip)
-char* error_buffer();
-constexpr int ERROR_BYTES = 512;
+// Host side of the geometry / grid units (defined in pntf_mesh.hip): both write the one
+// thread-local text behind pntf_mesh_last_error.  fail returns PNTF_ERR_ARG; check_launch
+// returns PNTF_ERR_HIP with "what: <HIP's text>" if a launch since the last call failed.
+int fail(const char* what);
+int check_launch(const char* what);
 
 constexpr int BLOCK = 256;       // lanes per workgroup = triangles per LDS tile
 constexpr int PTS = 4;           // points per lane, in registers
@@ -96,7 +100,7 @@ __device__ __forceinline__ float tri_d2(float px, float py, float pz,
   return inside ? fminf(h * h, e) : e;
 }
 
-// Exact tile culling, shared so both kernels skip by the same rule: a triangle whose AABB
+// Exact tile culling, shared so every kernel skips by the same rule: a triangle whose AABB
 // [bmin, bmax] is farther from the point box [lo, hi] than `bound` (a squared distance no
 // point of the box needs to beat) cannot lower a minimum.  Cull only with slack: gap^2 and
 // tri_d2 are both fp32-rounded, and a triangle whose true distance sits within a few ulp of
@@ -113,6 +117,22 @@ __device__ __forceinline__ bool tri_culled(float4 bmin, float4 bmax, const float
                                 fmaxf(fmaxf(fabsf(bmin.y), fabsf(bmax.y)),
                                       fmaxf(fabsf(bmin.z), fabsf(bmax.z)))), pext);
   return dot3(gx, gy, gz, gx, gy, gz) > bound * (1.f + 1e-4f) + 1e-6f * ext * ext;
+}
+
+// acc[i] = VALUE for i < n: the start of an atomic-min reduction
+template <class T, T VALUE>
+static __global__ void fill_kernel(T* __restrict__ acc, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) acc[i] = VALUE;
+}
+
+constexpr unsigned int D2_INF = 0x7f800000u;   // fp32 bits of d^2 = +inf
+
+// in place: fp32 bits of the minimum d^2 -> min(sqrt(d^2), cap); cap = INFINITY for none
+static __global__ void finalize_kernel(float* __restrict__ dist, int64_t n, float cap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    dist[i] = fminf(sqrtf(__uint_as_float(reinterpret_cast<unsigned int*>(dist)[i])), cap);
 }
 
 }  // namespace pntf_mesh

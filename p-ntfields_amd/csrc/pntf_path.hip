@@ -40,20 +40,6 @@ constexpr int SEGS = PTS;              // segments per lane (consecutive), SEGS 
 constexpr int SPW = BLOCK * SEGS;      // segments per workgroup
 constexpr u64 KEY_EMPTY = ((u64)0x7f800000u << 32) | 0xffffffffu;   // d^2 = +inf, where = -1
 
-int fail(const char* what) {
-  snprintf(error_buffer(), ERROR_BYTES, "%s", what);
-  return PNTF_ERR_ARG;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(error_buffer(), ERROR_BYTES, "%s: %s", what, hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
-}
-
 __device__ __forceinline__ float uniform(float v) {   // wave-uniform value -> SGPR
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
@@ -164,11 +150,6 @@ __global__ __launch_bounds__(BLOCK) void polyline_mesh_distance_kernel(
   }
 }
 
-__global__ void polyline_fill_kernel(u64* __restrict__ acc, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] = KEY_EMPTY;
-}
-
 // dist = min(cap, sqrt(d^2)); where = -1 when nothing was found or the cap decided (cap < d).
 // A distance equal to a finite cap > 0 to the bit is a tie between the two: dist is the cap
 // either way, where may be the segment or -1 (the cap also bounds the culling).
@@ -210,7 +191,7 @@ int pntf_polyline_mesh_distance(const float* pts, int64_t q, int32_t L, const in
   if (chunks > 65535) return fail("pntf_polyline_mesh_distance: more than 65535 segment chunks");
   u64* acc = reinterpret_cast<u64*>(ws);
   const unsigned g1 = (unsigned)((q + 255) / 256);
-  hipLaunchKernelGGL(polyline_fill_kernel, dim3(g1), dim3(256), 0, stream, acc, q);
+  hipLaunchKernelGGL((fill_kernel<u64, KEY_EMPTY>), dim3(g1), dim3(256), 0, stream, acc, q);
   if (chunks > 0)
     hipLaunchKernelGGL(polyline_mesh_distance_kernel, dim3((unsigned)q, (unsigned)chunks),
                        dim3(BLOCK), 0, stream, pts, L, cnt, tris, t, cap * cap, acc);

@@ -503,6 +503,75 @@ int pntf_grid_travel_time_pass(const float* speed, int32_t n, int64_t q, const f
                                float* Tout, int32_t inner, int32_t* changed,
                                hipStream_t stream);
 
+/* ---- Grid paths (pntf_gridpath.hip, pntf_grid_interp.h) -------------------------------- */
+
+/* The optimal baseline of a planned path: the minimum-time path out of a solved T, and the
+ * travel time of any polyline under the speed grid (not in the reference; used by
+ * p-ntfields_amd/pntf/evaluate.py path_optimality).  The grid is the solver's.  All arithmetic
+ * is fp32, one rounding per operation (nothing is contracted into an FMA), in the order
+ * written here.
+ *
+ * Interpolation of an array A (n, n, n) at a point x:
+ *   cell     per axis u = (clamp(x) + 0.5) (n - 1), clamp(x) = min(max(x, -0.5), 0.5) with the
+ *            min / max that return the operand that is a number, so that a NaN coordinate
+ *            lands in range too; i = min((int)u, n - 2), w = u - i in [0, 1].  No index ever
+ *            leaves [0, n - 2], whatever the input.
+ *   corners  l = 4 di + 2 dj + dk, di, dj, dk in {0, 1}: A_l = A[i + di, j + dj, k + dk], with
+ *            weights a_l = (di ? wx : 1 - wx), b_l = (dj ? wy : 1 - wy), c_l = (dk ? wz : 1 - wz).
+ *   sum8     of eight terms t_l: ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7)).
+ *   value    V(x) = sum8 of A_l ((a_l b_l) c_l): the trilinear blend.
+ *   gradient the exact gradient of that polynomial inside the cell:
+ *            dV/dx = (n - 1) sum8 of (di ? + : -) A_l (b_l c_l), and likewise dV/dy with
+ *            (a_l c_l) and the sign of dj, dV/dz with (a_l b_l) and the sign of dk: per axis
+ *            (n - 1) times the bilinear blend of the four corner differences along it.
+ *   blocked  a cell is blocked for A when any of its 8 corners is non-finite or, for the speed
+ *            array, <= 0.
+ *
+ * pntf_grid_descent: for each of q queries, the path from goal[c] down T[c] to src[c].
+ * T (q, n, n, n) is what the solver returned for src (q, 3) with init radius `radius` (>= 0);
+ * goal (q, 3); 0 < step <= 1 is the step length in units of h; pts (q, L, 3), L >= 2.
+ * With h = 1 / (n - 1), r = max(radius, 2) h, s = step h, x_s = clamp(src), per query:
+ *   x = clamp(goal); pts[0] = x; cnt = 1; tgoal = V_T(x), or +inf when x's cell is blocked in
+ *   T, which ends the query with status UNREACHABLE.  Then repeat:
+ *     if (dx dx + dy dy) + dz dz <= r r, d = x - x_s: ARRIVED.  x_s is appended unless x equals
+ *       it bit for bit (inside the init ball the solver's field is the straight line, so the
+ *       path closes with a straight segment); if that needs row L the status is TRUNCATED.
+ *     g = grad V_T(x), |g| = sqrt((gx gx + gy gy) + gz gz); |g| zero or non-finite: STALLED.
+ *     x' = clamp(x - s (g / |g|)), per axis.
+ *     x' in a cell blocked in T: BLOCKED.  Otherwise, unless V_T(x') < V_T(x): STALLED.
+ *     appending x' would need row L: TRUNCATED.  Otherwise append x' and go on from it.
+ * V_T falls strictly along the path, so it ends; every round appends a point or ends the query,
+ * so the kernel runs at most L rounds whatever T holds.  Rows of pts from cnt on are written
+ * as 0; 1 <= cnt <= L.  status, cnt (q) int32, tgoal (q).  A query's bits depend neither on the
+ * other queries of the batch, nor on its position in it, nor on L beyond truncation.
+ *
+ * pntf_grid_polyline_time: time[c] = travel time of polyline c (its first cnt[c] points of
+ * pts (q, L, 3), L >= 1; cnt clamped to 0..L) under speed (n, n, n).  Segment i from a to b has
+ * length len = sqrt((dx dx + dy dy) + dz dz), d = b - a, and is cut into
+ * m = min(max(1, ceil(len / (sub h))), 65536) equal pieces, sub > 0; piece p adds
+ * (len / m) / V_S(a + ((p + 0.5) / m) d), the midpoint rule, or +inf when the midpoint's cell
+ * is blocked in speed.  The midpoint is clamped to the box only by the lookup; lengths use the
+ * points as given.  A zero-length segment adds exactly 0, cnt <= 1 gives exactly 0, and a
+ * segment of non-finite length adds that length without a lookup.  Order: lane j of 256 adds
+ * the pieces of segments j, j + 256, ... in order to its own sum, and the 256 sums are added by
+ * the pairwise tree over adjacent lanes (1, 2, 4, ..., 128 apart).  A polyline's bits depend
+ * neither on L nor on the other rows.
+ *
+ * Limits: 2 <= n <= 1624 (the solver's), descent q <= 8 (2^31 - 1), polyline q < 2^31.  The
+ * host entry points cannot see the points; the torch wrappers reject non-finite ones.  Errors
+ * via pntf_mesh_last_error. */
+#define PNTF_DESCENT_ARRIVED 0
+#define PNTF_DESCENT_TRUNCATED 1
+#define PNTF_DESCENT_STALLED 2
+#define PNTF_DESCENT_BLOCKED 3
+#define PNTF_DESCENT_UNREACHABLE 4
+int pntf_grid_descent(const float* T, int32_t n, int64_t q, const float* src, const float* goal,
+                      float radius, float step, int32_t L, float* pts, int32_t* cnt,
+                      int32_t* status, float* tgoal, hipStream_t stream);
+int pntf_grid_polyline_time(const float* speed, int32_t n, const float* pts, int64_t q,
+                            int32_t L, const int32_t* cnt, float sub, float* time,
+                            hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

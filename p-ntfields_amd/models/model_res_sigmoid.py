@@ -356,6 +356,13 @@ class Model:
         raise ops.PntfError("FieldReport measures the field against a mesh in the workspace "
                             "(dim 3): not defined for the arm model")
 
+    def PlanOptimality(self, *args, **kwargs):
+        """The optimality report (pntf.evaluate.path_optimality) compares a path with fast
+        marching on a grid over the workspace; in joint space there is no such grid, so the arm
+        model raises, as its FieldReport does."""
+        raise ops.PntfError("PlanOptimality measures the path against a mesh in the workspace "
+                            "(dim 3): not defined for the arm model")
+
     def field_grid(self, limit=2.0):
         """The 80x80 evaluation grid of Model.plot (:1284-1311): start fixed at the reference's
         joint configuration Xsrc/(π/0.5), goal swept over [-limit, limit)^2 in the first two

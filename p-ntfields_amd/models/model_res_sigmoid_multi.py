@@ -401,6 +401,22 @@ class Model:
                                          sources.to(self._dev()), n=n, offset=offset,
                                          margin=margin, radius=radius)
 
+    def PlanOptimality(self, path, steps, tris, n=65, offset=None, margin=None, radius=4.0,
+                       step=0.5, chunk=64):
+        """How good the paths `Plan` returned are against the grid optimum
+        (pntf.evaluate.path_optimality): per query the planned polyline's travel time and length
+        under the true speed of the scene `tris` (t, 3, 3), the fast-marching optimum from its
+        start to its goal on n^3 nodes (ops.grid_travel_time, ops.grid_descent), the two ratios,
+        and floor_rel, the grid's own disagreement with itself.  A time_ratio within floor_rel
+        of 1 is not resolved at that n.  Workspace planning only (dim 3)."""
+        from pntf import evaluate
+        if self.dim != 3:
+            raise ops.PntfError("PlanOptimality measures the path against a mesh in the "
+                                "workspace: dim must be 3")
+        return evaluate.path_optimality(path.to(self._dev()), steps.to(self._dev()),
+                                        tris.to(self._dev()), n=n, offset=offset, margin=margin,
+                                        radius=radius, step=step, chunk=chunk)
+
     def field_grid(self, limit=0.5):
         """The 80x80 evaluation grid of Model.plot (:1250-1275): start fixed at
         (-0.25, -0.25, 0, ...), goal swept over [-limit, limit)^2 in the first two axes;

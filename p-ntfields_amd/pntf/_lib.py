@@ -148,7 +148,18 @@ SIGNATURES = {
                                                   _c_void_p, _c_void_p]),
     "pntf_grid_travel_time_pass": (ctypes.c_int, [_c_void_p, _i32, _i64, _c_void_p, _c_void_p,
                                                   _i32, _c_void_p, _c_void_p]),
+    # grid paths (pntf_gridpath.hip): T, n, q, src, goal, radius, step, L, pts, cnt, status,
+    # tgoal, stream / speed, n, pts, q, L, cnt, sub, time, stream
+    "pntf_grid_descent": (ctypes.c_int, [_c_void_p, _i32, _i64, _c_void_p, _c_void_p, _f32, _f32,
+                                         _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                         _c_void_p]),
+    "pntf_grid_polyline_time": (ctypes.c_int, [_c_void_p, _i32, _c_void_p, _i64, _i32, _c_void_p,
+                                               _f32, _c_void_p, _c_void_p]),
 }
+
+# pntf_grid_descent's status codes (include/pntf.h PNTF_DESCENT_*)
+DESCENT_ARRIVED, DESCENT_TRUNCATED, DESCENT_STALLED, DESCENT_BLOCKED, DESCENT_UNREACHABLE = \
+    range(5)
 
 _lib = None
 
@@ -189,7 +200,7 @@ def check(status, what):
         if what.startswith(("pntf_tt_", "pntf_adamw")):
             err = lib.pntf_tt_last_error()
         elif what.startswith(("pntf_point_mesh", "pntf_arm_mesh", "pntf_polyline_mesh",
-                              "pntf_grid_travel_time")):
+                              "pntf_grid_")):
             err = lib.pntf_mesh_last_error()
         else:
             err = lib.pntf_last_error()

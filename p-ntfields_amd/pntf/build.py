@@ -160,7 +160,8 @@ UNITS = (
     + [("util", "pntf_kernels.hip", ["-DPNTF_UTIL"]), ("capi", "pntf_capi.hip", []),
        ("train", "pntf_train.hip", []), ("gemm", "pntf_gemm.hip", []),
        ("mesh", "pntf_mesh.hip", []), ("arm", "pntf_arm.hip", []),
-       ("path", "pntf_path.hip", []), ("eikonal", "pntf_eikonal.hip", [])]
+       ("path", "pntf_path.hip", []), ("eikonal", "pntf_eikonal.hip", []),
+       ("gridpath", "pntf_gridpath.hip", [])]
 )
 
 

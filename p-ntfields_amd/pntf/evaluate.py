@@ -13,6 +13,11 @@ even when both its ends are clear.  For the arm (joint space) the clearance is S
 nodes of a grid over the box against the scene's ground truth — the speed from the exact
 point -> mesh distance, and the travel time from a grid Eikonal solve of that speed
 (ops.grid_travel_time) — together with the solver's own discretisation error at that grid.
+
+`path_optimality` says how good a successful path is: its travel time and length against the
+grid optimum — the minimum-time path out of that same grid solve (ops.grid_descent), both
+priced under the same speed grid (ops.grid_polyline_time) — with the grid's own resolution
+(`floor_rel`) beside the ratios.
 """
 import dataclasses
 import math
@@ -20,7 +25,7 @@ import math
 import torch
 
 from . import ops
-from ._lib import PntfError
+from ._lib import DESCENT_ARRIVED, PntfError
 
 ARM_SCALE = math.pi / 0.5     # normalised joint coordinates -> radians (test/arm_plan.py)
 
@@ -168,6 +173,92 @@ def field_report(travel_times, speed, tris, sources, n=65, offset=None, margin=N
             rows["tt_mean_rel"][c], rows["tt_max_rel"][c] = et.mean(), et.max()
             rows["floor_mean_rel"][c], rows["floor_max_rel"][c] = ef.mean(), ef.max()
     return FieldReport(converged=converged, passes=passes, T_grid=T, speed=S, **rows)
+
+
+@dataclasses.dataclass
+class PathOptimality:
+    """Per-query tensors (q,) on the device.  float64 rows are nan where undefined."""
+    time: torch.Tensor               # float64: travel time of the planned polyline
+    length: torch.Tensor             # float64: its length
+    optimal_time: torch.Tensor       # float64: the grid's T at the goal (tgoal)
+    optimal_path_time: torch.Tensor  # float64: travel time of the grid's own path
+    optimal_length: torch.Tensor     # float64: its length
+    time_ratio: torch.Tensor         # float64: time / optimal_time
+    length_ratio: torch.Tensor       # float64: length / optimal_length
+    status: torch.Tensor             # int32: the descent's status (0 = ARRIVED)
+    solve_converged: torch.Tensor    # bool: the grid solve reached its fixed point
+    floor_rel: torch.Tensor          # float64: |optimal_path_time - optimal_time| / optimal_time
+
+
+def path_optimality(path, steps, tris, n=65, offset=None, margin=None, radius=4.0, step=0.5,
+                    chunk=64):
+    """How good a planned path is against the grid optimum.  path (q, max_iter + 2, 6) and
+    steps (q,) as `ops.plan` returns them, `tris` (t, 3, 3) the obstacle mesh.  dim 3 only.
+
+    The baseline is fast marching on a grid, the one NTFields planners are judged against: the
+    scene's true speed at the n^3 nodes (ops.speed_grid, with field_report's defaults), the
+    grid travel time T from each query's start path[c, 0, :3] (ops.grid_travel_time, init radius
+    `radius`) and the minimum-time path from its goal path[c, 0, 3:] back down T
+    (ops.grid_descent, steps of step·h).  Both the planned polyline (ops.plan_polylines) and
+    the grid's path are priced under that same speed grid (ops.grid_polyline_time).  Queries
+    are solved `chunk` at a time, which bounds the solver's state at 2·chunk·n^3·4 bytes; the
+    result does not depend on chunk.  Per query:
+
+      time, length                 of the planned polyline (length: polyline_length)
+      optimal_time                 T interpolated at the goal
+      optimal_path_time, _length   of the grid's own path
+      time_ratio, length_ratio     time / optimal_time, length / optimal_length
+      status, solve_converged      of the descent (0 = ARRIVED) and of the grid solve
+      floor_rel                    |optimal_path_time - optimal_time| / optimal_time
+
+    floor_rel is the disagreement of the grid's own path with the grid's own T: two first-order
+    answers to the same question at this n, a few percent apart at n = 17..65.  It is the
+    resolution of the comparison: a time_ratio WITHIN floor_rel OF 1 IS NOT RESOLVED at this
+    n — raise n, do not read it as the planner beating or missing the optimum.  The float rows
+    are nan where undefined: the planned path's rows (time, length, both ratios) for steps -1
+    (invalid env), the optimum's rows (optimal_*, floor_rel, both ratios) for a descent that
+    did not ARRIVE or a non-finite optimum (a goal in a cell with a wall corner)."""
+    _require = ops._require_device
+    _require(path, "path")
+    _require(steps, "steps")
+    _require(tris, "tris")
+    if path.dim() != 3 or path.shape[2] != 6 or path.shape[1] < 1:
+        raise PntfError("path must be (q, rows, 6): the optimality report is defined for dim "
+                        "3, got %s" % (tuple(path.shape),))
+    if int(chunk) < 1:
+        raise PntfError("chunk must be >= 1")
+    margin = GIBSON_MARGIN if margin is None else float(margin)
+    offset = margin / 10.0 if offset is None else float(offset)
+    dev, n, q = path.device, int(n), path.shape[0]
+    path = path.detach().to(torch.float32)
+    ppts, pcnt = ops.plan_polylines(path, steps)
+    S = ops.speed_grid(tris.to(dev), n, offset, margin)
+    f64 = dict(dtype=torch.float64, device=dev)
+    opt_time, opt_path_time = torch.empty(q, **f64), torch.empty(q, **f64)
+    opt_length = torch.empty(q, **f64)
+    status = torch.empty(q, dtype=torch.int32, device=dev)
+    converged = torch.empty(q, dtype=torch.bool, device=dev)
+    for lo in range(0, q, int(chunk)):
+        sl = slice(lo, min(lo + int(chunk), q))
+        src, goal = path[sl, 0, :3].contiguous(), path[sl, 0, 3:].contiguous()
+        T, _, conv = ops.grid_travel_time(S, src, radius=radius)
+        dpts, dcnt, st, tgoal = ops.grid_descent(T, src, goal, radius=radius, step=step)
+        opt_time[sl], status[sl], converged[sl] = tgoal.to(torch.float64), st, conv
+        opt_path_time[sl] = ops.grid_polyline_time(S, dpts, dcnt).to(torch.float64)
+        opt_length[sl] = polyline_length(dpts, dcnt)
+    time = ops.grid_polyline_time(S, ppts, pcnt).to(torch.float64) if q else torch.empty(q, **f64)
+    length = polyline_length(ppts, pcnt)
+    opt = (status == DESCENT_ARRIVED) & torch.isfinite(opt_time) & torch.isfinite(opt_path_time)
+    planned = steps.to(dev) >= 0
+    nan = torch.full((q,), float("nan"), **f64)
+    rows = dict(optimal_time=(opt_time, opt), optimal_path_time=(opt_path_time, opt),
+                optimal_length=(opt_length, opt),
+                floor_rel=((opt_path_time - opt_time).abs() / opt_time, opt),
+                time=(time, planned), length=(length, planned),
+                time_ratio=(time / opt_time, planned & opt),
+                length_ratio=(length / opt_length, planned & opt))
+    rows = {k: torch.where(ok, v, nan) for k, (v, ok) in rows.items()}
+    return PathOptimality(status=status, solve_converged=converged, **rows)
 
 
 def arm_path_samples(pts, cnt, resolution, scale=ARM_SCALE):

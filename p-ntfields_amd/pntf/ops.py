@@ -22,7 +22,8 @@ __all__ = ["GRAD_EXACT", "GRAD_BACKGRAD_COMPAT", "PntfError", "pack_weights", "t
            "tau_grad", "path_velocity", "speed", "travel_time", "plan", "eikonal_residual",
            "device_sum", "packed_floats", "workspace_bytes", "point_mesh_distance",
            "arm_mesh_distance", "polyline_mesh_distance", "plan_polylines", "grid_travel_time",
-           "grid_travel_time_init", "grid_travel_time_pass", "grid_nodes", "speed_grid"]
+           "grid_travel_time_init", "grid_travel_time_pass", "grid_nodes", "speed_grid",
+           "grid_descent", "grid_polyline_time"]
 
 class StreamScratch:
     """Grow-only device scratch per (device, stream), least-recently-used first out.
@@ -574,3 +575,96 @@ def speed_grid(tris, n, offset, margin):
         raise PntfError("speed_grid: need n >= 2 and 0 <= offset <= margin, margin > 0")
     d = point_mesh_distance(grid_nodes(int(n), tris.device), tris)
     return (d.clamp(float(offset), float(margin)) / float(margin)).reshape(n, n, n)
+
+
+def _grid_points(p, q, what, name):
+    _require_device(p, name)
+    if p.dim() == 1:
+        p = p[None]
+    if p.dim() != 2 or p.shape[1] != 3 or (q is not None and p.shape[0] != q):
+        raise PntfError("%s: %s must be (q, 3)%s, got %s"
+                        % (what, name, "" if q is None else " with q = %d" % q, tuple(p.shape)))
+    return p.detach().to(torch.float32).contiguous()
+
+
+def grid_descent(T, src, goal, radius=4.0, step=0.5, max_points=None):
+    """The minimum-time paths out of solved grid travel times (pntf_grid_descent): T (q, n, n, n)
+    as `grid_travel_time` returned it for src (q, 3) with init radius `radius`, goal (q, 3) the
+    points to descend from.  From the goal, steps of step·h (0 < step <= 1, h = 1 / (n - 1))
+    against the gradient of the trilinear interpolant of T, until within max(radius, 2)·h of the
+    source, where the path closes with a straight segment (include/pntf.h).
+
+    Returns (pts (q, L, 3) float32 — row 0 the goal, rows past cnt zero —, cnt (q,) int32 >= 1,
+    status (q,) int32: 0 ARRIVED, 1 TRUNCATED (needed more than L rows), 2 STALLED (no descent:
+    a flat or non-finite gradient, or a step that did not lower T), 3 BLOCKED (stepped into a
+    cell with a +inf corner), 4 UNREACHABLE (the goal's own cell has one) —, tgoal (q,) float32:
+    the interpolated T at the goal, the optimal travel time, +inf when unreachable).
+    L = max_points defaults to ceil(4·(n - 1) / step) + 2.  A query's bits depend neither on the
+    batch nor on L beyond truncation.  Non-finite points raise PntfError before any launch."""
+    what = "grid_descent"
+    _require_device(T, "T")
+    if T.dim() != 4 or not (T.shape[1] == T.shape[2] == T.shape[3]) or T.shape[1] < 2:
+        raise PntfError("%s: T must be (q, n, n, n) with n >= 2, got %s" % (what, tuple(T.shape)))
+    q, n = T.shape[0], T.shape[1]
+    src = _grid_points(src, q, what, "src")
+    goal = _grid_points(goal, q, what, "goal")
+    if not (src.device == goal.device == T.device):
+        raise PntfError("%s: T, src and goal must be on the same device" % what)
+    step, radius = float(step), float(radius)
+    if not (0.0 < step <= 1.0):
+        raise PntfError("%s: step must be in (0, 1], got %r" % (what, step))
+    if not radius >= 0.0:
+        raise PntfError("%s: radius must be >= 0, got %r" % (what, radius))
+    L = int(np.ceil(4.0 * (n - 1) / step)) + 2 if max_points is None else int(max_points)
+    if L < 2:
+        raise PntfError("%s: max_points must be >= 2, got %d" % (what, L))
+    T = T.detach().to(torch.float32).contiguous()
+    dev = T.device
+    pts = torch.empty((q, L, 3), dtype=torch.float32, device=dev)
+    cnt = torch.empty(q, dtype=torch.int32, device=dev)
+    status = torch.empty(q, dtype=torch.int32, device=dev)
+    tgoal = torch.empty(q, dtype=torch.float32, device=dev)
+    if q == 0:
+        return pts, cnt, status, tgoal
+    if not bool(torch.isfinite(src).all()) or not bool(torch.isfinite(goal).all()):
+        raise PntfError("%s: src and goal must be finite" % what)
+    check(_lib.load().pntf_grid_descent(_vp(T), n, q, _vp(src), _vp(goal), radius, step, L,
+                                        _vp(pts), _vp(cnt), _vp(status), _vp(tgoal),
+                                        _stream(dev)), "pntf_grid_descent")
+    return pts, cnt, status, tgoal
+
+
+def grid_polyline_time(speed, pts, cnt, sub=0.5):
+    """Travel time (q,) float32 of the polylines pts (q, L, 3), cnt (q,) integers (the first
+    cnt[c] points, joined in order) under the node speed grid speed (n, n, n), on the HIP kernel
+    (pntf_grid_polyline_time): every segment is cut into pieces of at most sub·h (sub > 0) and
+    each piece adds its length over the trilinear speed at its midpoint.  +inf when a midpoint
+    falls in a cell with a wall (speed <= 0) corner; 0 for cnt <= 1.  Points outside the box
+    count with their full length at the speed of the nearest point of the box.  The bits depend
+    neither on L nor on the other rows.  Non-finite points raise PntfError before any launch."""
+    what = "grid_polyline_time"
+    speed = _grid_args(speed, what)
+    _require_device(pts, "pts")
+    _require_device(cnt, "cnt")
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise PntfError("%s: pts must be (q, L, 3), got %s" % (what, tuple(pts.shape)))
+    if cnt.dim() != 1 or cnt.shape[0] != pts.shape[0] or cnt.is_floating_point():
+        raise PntfError("%s: cnt must be (q,) integers, one per polyline, got %s %s"
+                        % (what, tuple(cnt.shape), cnt.dtype))
+    if not (pts.device == cnt.device == speed.device):
+        raise PntfError("%s: speed, pts and cnt must be on the same device" % what)
+    sub = float(sub)
+    if not (0.0 < sub < float("inf")):
+        raise PntfError("%s: sub must be > 0, got %r" % (what, sub))
+    q, L = pts.shape[0], pts.shape[1]
+    time = torch.zeros(q, dtype=torch.float32, device=pts.device)
+    if q == 0 or L == 0:
+        return time
+    pts = pts.detach().to(torch.float32).contiguous()
+    cnt = cnt.detach().to(torch.int32).contiguous()
+    if not bool(torch.isfinite(pts).all()):
+        raise PntfError("%s: pts must be finite" % what)
+    check(_lib.load().pntf_grid_polyline_time(_vp(speed), speed.shape[0], _vp(pts), q, L,
+                                              _vp(cnt), sub, _vp(time), _stream(pts.device)),
+          "pntf_grid_polyline_time")
+    return time

@@ -26,8 +26,8 @@ def _seg_d2(p, a, e):
 
 def tri_d2(p, tri):
     """Squared distance from points p (..., 3) to triangles tri (..., 3, 3), broadcasting;
-    Ericson §5.1.5 region tests; in the interior region a (near-)zero-area triangle
-    (sin^2 of the angle at a <= 1e-12, same test as the kernel) -> nearest edge."""
+    Ericson §5.1.5 region tests, the plane distance in the interior region; a (near-)zero-area
+    triangle (sin^2 of the angle at a <= 1e-12, same test as the kernel) -> nearest edge."""
     p = np.asarray(p, np.float64)
     a, b, c = tri[..., 0, :], tri[..., 1, :], tri[..., 2, :]
     ab, ac = b - a, c - a
@@ -60,8 +60,17 @@ def tri_d2(p, tri):
     r = p - q
     d2q = dot(r, r)
     n = np.cross(ab, ac)
-    flat = dot(n, n) <= 1e-12 * dot(ab, ab) * dot(ac, ac)
-    degen = ~(r1 | r2 | r3 | r4 | r5 | r6) & (~(s > 0) | flat)
+    nn = dot(n, n)
+    # Interior region: the plane distance, not |p - (a + v ab + w ac)|.  Ericson's v = vb / s
+    # and w = vc / s cancel to a relative 1e-16 / sin^2, which moved the closest point of a
+    # sliver (sin^2 ~ 1e-11) by up to 2e-6 of in-plane distance; the cross product cancels to
+    # 1e-16 / sin only (tests/test_mesh_conditioning.py pins this against long double).
+    interior = ~(r1 | r2 | r3 | r4 | r5 | r6)
+    d2q = np.where(interior & (nn > 0), dot(ap, n) ** 2 / safe(nn), d2q)
+    flat = nn <= 1e-12 * dot(ab, ab) * dot(ac, ac)
+    # A flat triangle is its three edges in EVERY region: with a == b the products above put
+    # every point of the a-c edge's region into "edge ab" (vc = 0), i.e. at the vertex a.
+    degen = flat | (interior & ~(s > 0))
     if np.any(degen):
         de = np.minimum(np.minimum(_seg_d2(p, a, ab), _seg_d2(p, a, ac)), _seg_d2(p, b, c - b))
         d2q = np.where(degen, de, d2q)

@@ -30,10 +30,32 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 // Per-triangle record staged in LDS (8 float4, built once per tile by one lane each):
 //   [0] a, 1/|ab|^2   [1] ab, 1/|ac|^2   [2] ac, 1/|bc|^2   [3] bc, flat
 //   [4] n^ (unit normal)   [5] m_ab = n^ x ab   [6] m_ac = ac x n^   [7] m_bc = n^ x bc
-// m_* are in-plane edge normals pointing into the triangle; `flat` = 1 for a (near-)zero-area
-// triangle (sin^2 of the angle at a <= 1e-12), whose distance is then its nearest edge.
+// m_* are in-plane edge normals pointing into the triangle, each with w = -INSIDE_TAU |m|;
+// `flat` = 1 for a (near-)zero-area triangle (sin^2 of the angle at a <= 1e-12), whose
+// distance is then its nearest edge.
 //   [8] triangle AABB min   [9] triangle AABB max   (tile culling, see the kernels)
+//
+// Conditioning.  The cross product of a thin triangle (sine of the angle at a = s) cancels to
+// |ab||ac|s, so in fp32 the direction of n^ is off by ~6e-8 / s and the plane distance q.n^ by
+// |q| times that — 1e-5 at s = 1e-3, and almost always too small, which then wins tri_d2's
+// min.  Where the fp32 cross product says sin^2 <= THIN_SIN2 (s <= 0.03; it still has five
+// digits there), or gives nothing usable (zero, underflow), n^ and `flat` are taken again from
+// the exact fp64 edge differences of the fp32 vertices and rounded to fp32 once: ~1e-16 / s,
+// below the final rounding for every triangle that is not `flat`.  Above the threshold the
+// fp32 normal keeps its bits; it is off by at most 6e-8 / 0.03 = 2e-6 of the query's in-plane
+// distance from a (measured at s = 0.01 before the switch: 3e-7 at most).  About one triangle
+// in 2000 of a random mesh is that thin at a, so few waves take the branch.
+//
+// The inside test of tri_d2 is q.m >= INSIDE_TAU |m| for the three edges, not >= 0: q = p - a
+// carries an fp32 rounding of ~6e-8 |q|, and where two edges meet at an angle s a point of the
+// plane up to that rounding / s BEYOND the tip passed all three tests at 0 and got the plane
+// distance (~0) instead of its distance to the tip.  A point within INSIDE_TAU of an edge,
+// seen from inside, now takes the edge distance, which is at most INSIDE_TAU farther than the
+// plane distance.  INSIDE_TAU covers the roundings of q, m and the dot product (about
+// 8 x 2^-24 |q||m|) for |q| <= 0.5.
 constexpr int REC = 10;
+constexpr float INSIDE_TAU = 2.5e-7f;
+constexpr float THIN_SIN2 = 1e-3f;
 
 __device__ __forceinline__ void build_record(const float* __restrict__ t, float4* __restrict__ r) {
   const float ax = t[0], ay = t[1], az = t[2];
@@ -45,17 +67,31 @@ __device__ __forceinline__ void build_record(const float* __restrict__ t, float4
   const float bc2 = dot3(bcx, bcy, bcz, bcx, bcy, bcz);
   float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
   const float nn = dot3(nx, ny, nz, nx, ny, nz);
-  const bool flat = !(nn > 1e-12f * ab2 * ac2);
+  bool flat = !(nn > 1e-12f * ab2 * ac2);
   const float inv = flat ? 0.f : 1.f / sqrtf(nn);
   nx *= inv; ny *= inv; nz *= inv;
+  if (!(nn > THIN_SIN2 * ab2 * ac2)) {  // thin at a, flat, or too small for fp32: fp64 normal
+    const double dabx = (double)t[3] - ax, daby = (double)t[4] - ay, dabz = (double)t[5] - az;
+    const double dacx = (double)t[6] - ax, dacy = (double)t[7] - ay, dacz = (double)t[8] - az;
+    const double dnx = daby * dacz - dabz * dacy, dny = dabz * dacx - dabx * dacz,
+                 dnz = dabx * dacy - daby * dacx;
+    const double dnn = fma(dnx, dnx, fma(dny, dny, dnz * dnz));
+    flat = !(dnn > 1e-12 * fma(dabx, dabx, fma(daby, daby, dabz * dabz)) *
+                       fma(dacx, dacx, fma(dacy, dacy, dacz * dacz)));
+    const double dinv = flat ? 0.0 : 1.0 / sqrt(dnn);
+    nx = (float)(dnx * dinv); ny = (float)(dny * dinv); nz = (float)(dnz * dinv);
+  }
+  const float wab = -INSIDE_TAU * __builtin_amdgcn_sqrtf(ab2),
+              wac = -INSIDE_TAU * __builtin_amdgcn_sqrtf(ac2),
+              wbc = -INSIDE_TAU * __builtin_amdgcn_sqrtf(bc2);
   r[0] = make_float4(ax, ay, az, ab2 > 0.f ? 1.f / ab2 : 0.f);
   r[1] = make_float4(abx, aby, abz, ac2 > 0.f ? 1.f / ac2 : 0.f);
   r[2] = make_float4(acx, acy, acz, bc2 > 0.f ? 1.f / bc2 : 0.f);
   r[3] = make_float4(bcx, bcy, bcz, flat ? 1.f : 0.f);
   r[4] = make_float4(nx, ny, nz, 0.f);
-  r[5] = make_float4(ny * abz - nz * aby, nz * abx - nx * abz, nx * aby - ny * abx, 0.f);
-  r[6] = make_float4(acy * nz - acz * ny, acz * nx - acx * nz, acx * ny - acy * nx, 0.f);
-  r[7] = make_float4(ny * bcz - nz * bcy, nz * bcx - nx * bcz, nx * bcy - ny * bcx, 0.f);
+  r[5] = make_float4(ny * abz - nz * aby, nz * abx - nx * abz, nx * aby - ny * abx, wab);
+  r[6] = make_float4(acy * nz - acz * ny, acz * nx - acx * nz, acx * ny - acy * nx, wac);
+  r[7] = make_float4(ny * bcz - nz * bcy, nz * bcx - nx * bcz, nx * bcy - ny * bcx, wbc);
   r[8] = make_float4(fminf(ax, fminf(t[3], t[6])), fminf(ay, fminf(t[4], t[7])),
                      fminf(az, fminf(t[5], t[8])), 0.f);
   r[9] = make_float4(fmaxf(ax, fmaxf(t[3], t[6])), fmaxf(ay, fmaxf(t[4], t[7])),
@@ -81,6 +117,12 @@ __device__ __forceinline__ float seg_d2(float qx, float qy, float qz, float4 e, 
   return dot3(rx, ry, rz, rx, ry, rz);
 }
 
+// q.m - INSIDE_TAU |m| for an in-plane edge normal of the record (the offset rides in m.w, so
+// the test costs what q.m >= 0 did)
+__device__ __forceinline__ float side(float qx, float qy, float qz, float4 m) {
+  return fmaf(qx, m.x, fmaf(qy, m.y, fmaf(qz, m.z, m.w)));
+}
+
 // Branch-free |p - closest point of the triangle|^2: if p projects inside the triangle the
 // distance is the plane distance, otherwise the nearest of the three edges (exactly the
 // Voronoi regions of Ericson §5.1.5, evaluated without divergence: every lane of a wave
@@ -94,9 +136,8 @@ __device__ __forceinline__ float tri_d2(float px, float py, float pz,
   e = fminf(e, seg_d2(bx, by, bz, bc, ac.w));
   const float4 n = r[4], m0 = r[5], m1 = r[6], m2 = r[7];
   const float h = dot3(qx, qy, qz, n.x, n.y, n.z);
-  const bool inside = dot3(qx, qy, qz, m0.x, m0.y, m0.z) >= 0.f &&
-                      dot3(qx, qy, qz, m1.x, m1.y, m1.z) >= 0.f &&
-                      dot3(bx, by, bz, m2.x, m2.y, m2.z) >= 0.f && bc.w == 0.f;
+  const bool inside = side(qx, qy, qz, m0) >= 0.f && side(qx, qy, qz, m1) >= 0.f &&
+                      side(bx, by, bz, m2) >= 0.f && bc.w == 0.f;
   return inside ? fminf(h * h, e) : e;
 }
 

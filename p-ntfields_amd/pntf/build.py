@@ -172,13 +172,20 @@ def hipcc():
     return "hipcc"
 
 
+def _flags_id(*parts):
+    """repr of flags / defines for hashing, with the checkout's own path taken out: the -I
+    flags are absolute, and an id that changed with the directory the tree lives in made a
+    library built in one place look stale in a copy of the same sources elsewhere."""
+    return repr(parts).replace(REPO, "<repo>").encode()
+
+
 def _stamp():
     h = hashlib.sha256()
     for d in (CSRC, INCLUDE):
         for name in sorted(os.listdir(d)):
             with open(os.path.join(d, name), "rb") as fh:
                 h.update(name.encode() + fh.read())
-    h.update(repr((CXXFLAGS, UNITS)).encode())
+    h.update(_flags_id(CXXFLAGS, UNITS))
     return h.hexdigest()
 
 
@@ -197,7 +204,7 @@ def unit_ids():
         h = hdr.copy()
         with open(os.path.join(CSRC, src), "rb") as fh:
             h.update(fh.read())
-        h.update(repr((CXXFLAGS, defs)).encode())
+        h.update(_flags_id(CXXFLAGS, defs))
         ids[name] = h.hexdigest()[:16]
     return ids
 

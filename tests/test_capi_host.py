@@ -275,6 +275,25 @@ def test_build_info_names_every_kernel_unit():
     assert info == build.unit_ids()          # the loaded library is the current source
 
 
+def test_unit_ids_do_not_depend_on_where_the_tree_lives(tmp_path):
+    """The -I flags are absolute; the ids hash them with the checkout's path taken out, so a
+    library built in one directory matches a copy of the same sources in another."""
+    import importlib.util
+    import shutil
+    from pntf import build
+    pkg = tmp_path / "p-ntfields_amd"
+    shutil.copytree(build.CSRC, pkg / "csrc")
+    shutil.copytree(build.INCLUDE, tmp_path / "include")
+    (pkg / "pntf").mkdir()
+    shutil.copy(os.path.join(build.PKG, "build.py"), pkg / "pntf" / "build.py")
+    spec = importlib.util.spec_from_file_location("moved_build", pkg / "pntf" / "build.py")
+    moved = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(moved)
+    assert moved.REPO == str(tmp_path) != build.REPO and moved.CXXFLAGS != build.CXXFLAGS
+    assert moved.unit_ids() == build.unit_ids()
+    assert moved._stamp() == build._stamp()
+
+
 def _asm(unit):
     from pntf import build
     import glob

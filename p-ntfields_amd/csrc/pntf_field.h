@@ -34,13 +34,24 @@ namespace pntf {
 // softplus_10 with torch's threshold (Softplus(beta=10), :140) and σ(10y) from one exp.
 // Written with hardware v_exp/v_log/v_rcp and selects only: a branch (or an IEEE divide)
 // here would split the unrolled MFMA stream and force spills.
-__device__ __forceinline__ float exp_neg10abs(float y) {   // exp(-10|y|) in (0, 1]
+// Each primitive of this section is called on its own by tests/prim_probe.hip and held against
+// fp64 by tests/test_device_primitives.py (bounds and measured ratios: DESIGN.md §4, "Device
+// primitives, one by one"); the claims in the comments below are the ones those tests assert.
+__device__ __forceinline__ float exp_neg10abs(float y) {   // exp(-10|y|) in [0, 1]
+  // v_exp_f32 flushes: exactly 0 once 10|y|/ln 2 > 126 (|y| > 8.73), so t is 0 or normal
   return __builtin_amdgcn_exp2f(-14.4269504088896341f * fabsf(y));
 }
-// log1p(t) for t in [0, 1] as log(1 + t): absolute error <= 2^-24, i.e. <= 6e-9 after the
-// 1/10 of softplus_10 — far below the fp32 rounding of the activations it is added to.
+// The rounding error of u = fl(1 + t), t in [0, 1]: e = (1 + t) - u exactly (Fast2Sum, 1 >= t).
+// log(1 + t) = log(u) + log(1 + e/u), and e stands in for log(1 + e/u): the difference is below
+// |e|·t <= 2^-24·t, under one eps32 of log(1 + t) >= 0.69 t.  Without it log(u) alone is right
+// only to an absolute 2^-24 — exactly 0 for every t <= 2^-24 — which is a relative error where
+// the log term stands alone: softplus_10(y) for y < 0, the merge where max(zs, zg) is 0
+// (tests/test_device_primitives.py *_softplus_bound, test_merge_max_min_bound).
+__device__ __forceinline__ float one_plus_err(float t, float u) { return t - (u - 1.f); }
+// log1p(t) for t in [0, 1], fp32-relative
 __device__ __forceinline__ float log1p_small(float t) {
-  return __builtin_amdgcn_logf(1.f + t) * 0.693147180559945309f;
+  const float u = 1.f + t;
+  return fmaf(__builtin_amdgcn_logf(u), 0.693147180559945309f, one_plus_err(t, u));
 }
 struct SpSig {
   float sp, sg;
@@ -55,9 +66,14 @@ __device__ __forceinline__ SpSig sp_sig(float y) {
   bool pos = y >= 0.f;
   SpSig o;
   // softplus_10(y) = max(y, 0) + log(1 + e^{-10|y|}) / 10, with log2 → ln and the 1/10
-  // folded into one constant.  torch returns y itself above 10y > 20; there the log term is
-  // < 2.1e-10 < ulp(y)/2, so the same expression rounds to exactly y without a select.
-  o.sp = fmaf(__builtin_amdgcn_logf(u), 0.0693147180559945309f, pos ? y : 0.f);
+  // folded into one constant, and the rounding error of 1 + t added back (one_plus_err) so
+  // that the value is fp32-relative for y < 0 too.  torch returns y itself above 10y > 20; no
+  // select is needed for that: from 10|y| >= 24 ln 2 = 16.64 on, u rounds to exactly 1, the log
+  // is exactly 0, and t/10 < 2.1e-10 is far below ulp(y)/2: sp is y bit for bit (tested).
+  o.sp = fmaf(__builtin_amdgcn_logf(u), 0.0693147180559945309f,
+              fmaf(one_plus_err(t, u), 0.1f, pos ? y : 0.f));
+  // σ(10y) in [0, 1]: r = 1/u <= 1 and t·r <= 1/2; exactly 1 / 0 once t has flushed, and
+  // σ(y) + σ(-y) = r + t·r is within 2 eps32 of 1 (tested)
   o.sg = pos ? r : t * r;
   return o;
 }
@@ -68,9 +84,39 @@ __device__ __forceinline__ float sig10(float y) {
   return (y >= 0.f) ? r : t * r;
 }
 
+// The start/goal merge of one feature (:236-244): smooth max M and min m of (zs, zg),
+// max/min ± log1p(e^{-10|zs - zg|}) / 10, and the switch s0 = σ(10 (zs - zg)) of its Jacobian.
+struct Merge {
+  float M, m, s0;
+};
+__device__ __forceinline__ Merge smooth_merge(float zs, float zg) {
+  float d = zs - zg;
+  float e = exp_neg10abs(d);
+  float cc = 0.1f * log1p_small(e);
+  Merge o;
+  o.M = fmaxf(zs, zg) + cc;
+  o.m = fminf(zs, zg) - cc;
+  float rr = __builtin_amdgcn_rcpf(1.f + e);
+  o.s0 = (d >= 0.f) ? rr : e * rr;
+  return o;
+}
+
+// The head's σ(0.1 y) (:254-255): 1 / (1 + 2^{-0.1 y / ln 2}).  No select: for y << 0 the exp2
+// overflows to +inf and rcp(inf) = 0, for y >> 0 it flushes to 0 and rcp(1) = 1.
+__device__ __forceinline__ float head_sig(float y4) {
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-0.144269504088896341f * y4));
+}
+
 // Branch-free sincos for the Fourier features: Cody-Waite reduction by 2π (hi/lo split),
-// then the hardware v_sin/v_cos on |r| <= π (input in revolutions).  The libm sincosf
-// carries a Payne-Hanek slow path whose branches split the unrolled MFMA stream.
+// then the hardware v_sin/v_cos (input in revolutions).  The libm sincosf carries a
+// Payne-Hanek slow path whose branches split the unrolled MFMA stream.
+// The reduction evaluated exactly (tests/prim_oracle.py reduce_exact): k is the nearest
+// revolution only up to the rounding of q/2π, so |r| <= π + eps32·|q| — not π: q = fl(π)
+// already gives k = 0, r = q > π — which v_sin/v_cos (valid to ±256 revolutions) absorb;
+// r differs from q - 2πk by less than eps32·|q| (both fmas are exact products with one
+// rounding each, and fp32(2π) + lo is 2π to 7e-15).  Both hold, with |r| <= 3π/2, for every
+// |q| <= Q = 2^24, where ulp(q) reaches 2 rad; the workload's |q| stays below about 30.
+// Beyond Q the results are still finite and in [-1, 1] but k drifts off the nearest revolution.
 __device__ __forceinline__ void sincos_fast(float q, float& s, float& c) {
   const float inv2pi = 0.159154943091895336f;
   float k = rintf(q * inv2pi);
@@ -752,14 +798,10 @@ __device__ __forceinline__ float forward_pass(Ring& ring, const float* __restric
     f32x4 s0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float zs = Y[t][r], zg = Y[8 + t][r];
-      float d = zs - zg;
-      float e = exp_neg10abs(d);
-      float cc = 0.1f * log1p_small(e);
-      X[t][r] = fmaxf(zs, zg) + cc;
-      X[8 + t][r] = fminf(zs, zg) - cc;
-      float rr = __builtin_amdgcn_rcpf(1.f + e);
-      s0[r] = (d >= 0.f) ? rr : e * rr;
+      const Merge u = smooth_merge(Y[t][r], Y[8 + t][r]);
+      X[t][r] = u.M;
+      X[8 + t][r] = u.m;
+      s0[r] = u.s0;
     }
     if (GRAD) store_tile(sc, T_S0 + t, lane, s0);
   }
@@ -801,7 +843,7 @@ __device__ __forceinline__ float forward_pass(Ring& ring, const float* __restric
   part += __shfl_xor(part, 32);
   float y4 = part + g4b;
   PNTF_STAMP(15);
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-0.144269504088896341f * y4));
+  return head_sig(y4);
 }
 
 // Reverse sweep: exact reverse mode, or NN.out_backgrad when the forward stored the quirk.

@@ -471,7 +471,7 @@ __device__ __forceinline__ float quad_forward(QRing<QR>& ring, Rsrc W, const QCx
   });
   qreduce<1>(cx, part);
   const float y4 = part[0] + aux[13][QAUX_G4B];
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-0.144269504088896341f * y4));
+  return head_sig(y4);
 }
 
 // Reverse sweep (exact, or out_backgrad when the forward stored the quirk): dτ/dxs, dτ/dxg of

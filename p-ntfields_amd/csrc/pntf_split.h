@@ -311,14 +311,10 @@ __device__ __forceinline__ float split_forward(Ring& ring, const float* __restri
     f32x4 s0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float zs = X[t][r], zg = X[8 + t][r];
-      float d = zs - zg;
-      float e = exp_neg10abs(d);
-      float cc = 0.1f * log1p_small(e);
-      X[t][r] = fmaxf(zs, zg) + cc;
-      X[8 + t][r] = fminf(zs, zg) - cc;
-      float rr = __builtin_amdgcn_rcpf(1.f + e);
-      s0[r] = (d >= 0.f) ? rr : e * rr;
+      const Merge u = smooth_merge(X[t][r], X[8 + t][r]);
+      X[t][r] = u.M;
+      X[8 + t][r] = u.m;
+      s0[r] = u.s0;
     }
     if (GRAD) store_tile(sc, T_S0 + t, lane, s0);
   }
@@ -374,7 +370,7 @@ __device__ __forceinline__ float split_forward(Ring& ring, const float* __restri
   part[0] += __shfl_xor(part[0], 32);
   reduce_waves<1>(sp, part);
   const float y4 = part[0] + g4b;
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-0.144269504088896341f * y4));
+  return head_sig(y4);
 }
 
 // Split reverse sweep (exact, or out_backgrad when the forward stored the quirk).  On entry

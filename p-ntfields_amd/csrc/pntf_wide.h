@@ -104,6 +104,11 @@ __device__ __forceinline__ f32x16 wx6_mma(const f32x4& w0, const f32x4& w1, cons
 // scaling multiply and softplus₁₀'s log term no constant: κ·softplus₁₀(y) = max(y', 0) +
 // log₂(1 + 2^{-|y'|}); σ(10 y) is unchanged, so the reverse sweep (σ tiles, unscaled Wᵀ) is
 // as before.  One VALU op fewer per activation element (tests/diag ablation: -0.5 %).
+// Tested on their own (tests/test_device_primitives.py): wx6_split's terms equal
+// the RNE split bit for bit, wx6_mma issues exactly the six products (planted operands make a
+// dropped one a gross error), and wsp_sig(fl(κ·y)) holds σ(10y) and, times ln 2 / 10,
+// softplus₁₀(y) to 8·eps32·A with the rounding of κ·y counted in A; for y' >= 24 (10y >= 16.64)
+// 1 + 2^{-y'} rounds to 1 and sp' is y' bit for bit.
 constexpr float WKAPPA = WIDE_KAPPA;                  // 10 / ln 2
 constexpr float WKAPPA_INV = 0.0693147180559945309f;  // ln 2 / 10
 __device__ __forceinline__ SpSig wsp_sig(float y) {   // y = κ·(pre-activation)
@@ -115,7 +120,9 @@ __device__ __forceinline__ SpSig wsp_sig(float y) {   // y = κ·(pre-activation
   const float r = __builtin_amdgcn_rcpf(u);
   const bool pos = y >= 0.f;
   SpSig o;
-  o.sp = (pos ? y : 0.f) + __builtin_amdgcn_logf(u);   // κ·softplus₁₀ (log2: v_log_f32)
+  // κ·softplus₁₀ (log2: v_log_f32), with the rounding error of 1 + t added back (pntf_field.h
+  // one_plus_err; 1/ln 2 turns it into log2) so that the value is fp32-relative for y < 0 too
+  o.sp = fmaf(one_plus_err(t, u), 1.44269504088896341f, pos ? y : 0.f) + __builtin_amdgcn_logf(u);
   o.sg = pos ? r : t * r;
   return o;
 }
@@ -735,10 +742,11 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
       float zs = Y[t][r], zg = Y[4 + t][r];   // κ-scaled
       float d = zs - zg;
       float e = __builtin_amdgcn_exp2f(-fabsf(d));    // e^{-10|zs - zg|}
-      float cc = __builtin_amdgcn_logf(1.f + e);      // κ·0.1·ln(1 + e)
+      float ue = 1.f + e;                             // κ·0.1·ln(1 + e), as wsp_sig's log term
+      float cc = fmaf(one_plus_err(e, ue), 1.44269504088896341f, __builtin_amdgcn_logf(ue));
       X[t][r] = fmaxf(zs, zg) + cc;
       X[4 + t][r] = fminf(zs, zg) - cc;
-      float rr = __builtin_amdgcn_rcpf(1.f + e);
+      float rr = __builtin_amdgcn_rcpf(ue);
       s0[r] = (d >= 0.f) ? rr : e * rr;
     }
     if (GRAD) lstore(wl, WL_S0 + t, s0);
@@ -787,7 +795,7 @@ __device__ __forceinline__ float wide_forward_x(Ring& ring, Rsrc W, const PairIO
     }
   part += __shfl_xor(part, 32);
   const float y4 = fmaf(part, WKAPPA_INV, bload(W, 0, WG4B)[0]);   // part = κ·(g4w·h3)
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-0.144269504088896341f * y4));
+  return head_sig(y4);
 }
 
 // ---------------------------------------------------------------- reverse sweep

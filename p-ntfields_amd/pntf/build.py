@@ -119,7 +119,10 @@ SGPR_SPILL_FREE = re.compile(r"^wide_d\d_k[014]$")
 # quad kernels run 8 waves with a 16-fragment ring (the 4-wave SOLO planner kept 2 beside its
 # 32-fragment ring; with -DPNTF_QWAVES=4 raise these back to 2).
 QRING_MFMA, QRING_SOLO = 16, 22   # quad weight-ring depths (fragments per wave)
-VGPR_SPILL_ALLOWED = {"plan_quad_solo_d3": 0, "plan_quad_solo_d6": 0}
+# field_d6_k2 / k3 and residual_d3 sit at 256 VGPRs; the rounding-error term of softplus_10's
+# log (pntf_field.h one_plus_err) costs each of them 2 copies into AGPRs (ScratchSize 0).
+VGPR_SPILL_ALLOWED = {"plan_quad_solo_d3": 0, "plan_quad_solo_d6": 0,
+                      "field_d6_k2": 2, "field_d6_k3": 2, "residual_d3": 2}
 
 UNITS = (
     [("field_d%d_k%d" % (d, k), "pntf_kernels.hip", ["-DPNTF_DIM=%d" % d, "-DPNTF_KIND=%d" % k])

@@ -34,19 +34,13 @@ namespace pntf_gemm {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef PNTF_GEMM_BK
-#define PNTF_GEMM_BK 8
-#endif
-#ifndef PNTF_GEMM_SPLITS
-#define PNTF_GEMM_SPLITS 512
-#endif
-#ifndef PNTF_GEMM_BM
-#define PNTF_GEMM_BM 128
-#endif
-constexpr int BM = PNTF_GEMM_BM, BN = 128, BK = PNTF_GEMM_BK;   // BN: the narrowest tile
-constexpr int RB = BM / 64;          // 32-row MFMA blocks per wave (waves are 2 x 2)
+// workgroup tile BM x BN, K chunks of BK (chunks of 8 beat 16 and 32, header)
+constexpr int BM = 128, BN = 128, BK = 8;
+constexpr int RB = BM / 64, CB = BN / 64;   // 32-row / 32-column MFMA blocks per wave (2 x 2 waves)
 constexpr int GLA = BM * BK / 1024;  // float4 global loads per lane per chunk: A
+constexpr int GLB = BN * BK / 1024;  // ... and B
 constexpr int LSA = BM + 32;         // LDS row strides (≡ 32 mod 64: conflict-free halves)
+constexpr int LSB = BN + 32;
 
 struct GemmArgs {
   const float* A;
@@ -57,18 +51,15 @@ struct GemmArgs {
   float beta;
 };
 
-template <bool TA, bool TB, int BNT>
+template <bool TA, bool TB>
 __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
-  constexpr int GLB = BNT * BK / 1024;   // float4 global loads per lane per chunk: B
-  constexpr int LSB = BNT + 32;          // ≡ 32 mod 64, like LSA
-  constexpr int CB = BNT / 64;           // 32-column MFMA blocks per wave
   __shared__ float As[2][BK * LSA];
   __shared__ float Bs[2][BK * LSB];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = w & 1, wn = w >> 1;
   const int64_t m0 = (int64_t)blockIdx.y * BM;
-  const int64_t n0 = (int64_t)blockIdx.x * BNT;
+  const int64_t n0 = (int64_t)blockIdx.x * BN;
   const int64_t kb = (int64_t)blockIdx.z * g.kper;
   const int64_t ke = kb + g.kper < g.K ? kb + g.kper : g.K;
   const int nchunks = (int)((ke - kb + BK - 1) / BK);
@@ -92,10 +83,10 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
     for (int i = 0; i < GLB; ++i) {
       const int idx = t + 256 * i;
       if (TB) {
-        const int n = idx % BNT, k = 4 * (idx / BNT);
+        const int n = idx % BN, k = 4 * (idx / BN);
         rb[i] = *reinterpret_cast<const f32x4*>(g.B + (n0 + n) * g.ldb + k0 + k);
       } else {
-        const int k = idx / (BNT / 4), n = 4 * (idx % (BNT / 4));
+        const int k = idx / (BN / 4), n = 4 * (idx % (BN / 4));
         rb[i] = *reinterpret_cast<const f32x4*>(g.B + (k0 + k) * g.ldb + n0 + n);
       }
     }
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
     for (int i = 0; i < GLB; ++i) {
       const int idx = t + 256 * i;
       if (TB) {   // B(k, n) = B[n·ldb + k]: float4 along k, consecutive lanes on consecutive n
-        const int n = idx % BNT, k = 4 * (idx / BNT);
+        const int n = idx % BN, k = 4 * (idx / BN);
         const int64_t gk = k0 + k, gn = n0 + n;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (gk + 3 < ke) {
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
         }
         rb[i] = v;
       } else {    // B(k, n) = B[k·ldb + n]: float4 along n
-        const int k = idx / (BNT / 4), n = 4 * (idx % (BNT / 4));
+        const int k = idx / (BN / 4), n = 4 * (idx % (BN / 4));
         const int64_t gk = k0 + k;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (gk < ke) v = *reinterpret_cast<const f32x4*>(g.B + gk * g.ldb + n0 + n);
@@ -179,11 +170,11 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
     for (int i = 0; i < GLB; ++i) {
       const int idx = t + 256 * i;
       if (TB) {
-        const int n = idx % BNT, k = 4 * (idx / BNT);
+        const int n = idx % BN, k = 4 * (idx / BN);
 #pragma unroll
         for (int e = 0; e < 4; ++e) Bs[buf][(k + e) * LSB + n] = rb[i][e];
       } else {
-        const int k = idx / (BNT / 4), n = 4 * (idx % (BNT / 4));
+        const int k = idx / (BN / 4), n = 4 * (idx % (BN / 4));
         *reinterpret_cast<f32x4*>(&Bs[buf][k * LSB + n]) = rb[i];
       }
     }
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
     lstore(0);
   }
   __syncthreads();
-  const int am = wm * (BM / 2) + (lane & 31), bn = wn * (BNT / 2) + (lane & 31), kh = lane >> 5;
+  const int am = wm * (BM / 2) + (lane & 31), bn = wn * (BN / 2) + (lane & 31), kh = lane >> 5;
   for (int c = 0; c < nchunks; ++c) {
     const int buf = c & 1;
     const bool more = c + 1 < nchunks;
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel(GemmArgs g) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        const int64_t col = n0 + wn * (BNT / 2) + 32 * j + (lane & 31);
+        const int64_t col = n0 + wn * (BN / 2) + 32 * j + (lane & 31);
         if (row < g.M) {
           if (split) {
             g.work[((int64_t)blockIdx.z * g.M + row) * g.N + col] = acc[i][j][r];
@@ -299,18 +290,9 @@ __global__ void gemm_reduce2_kernel(const float* __restrict__ work, int splits, 
 // its last use in the last group, so the panel double-buffers in place.  Persistent waves,
 // one per SIMD (≤ 512 VGPRs), grid-stride over 32-row tiles.  ACC adds C (the residual
 // branch's gradient, beta = 1), loaded 4 iterations before the group's store.
-#ifndef PNTF_PANEL_PF
-#define PNTF_PANEL_PF 3
-#endif
-// diagnostic builds only (tests/diag/panel_variants.py): bit 1 = no next-panel loads (every
-// tile reuses the first panel), bit 2 = no C stores, bit 4 = no fragment loads (ring reuse)
-// waves per SIMD (workgroups per CU): 1 keeps ≤ 512 registers per wave
-#ifndef PNTF_PANEL_WPS
-#define PNTF_PANEL_WPS 1
-#endif
-#ifndef PNTF_PANEL_DIAG
-#define PNTF_PANEL_DIAG 0
-#endif
+// One wave per SIMD (one workgroup per CU) keeps ≤ 512 registers per wave.  Tried: builds without
+// the next-panel loads, the C stores or the fragment loads (profiles/r02_panel_variants.log).
+constexpr int PANEL_PF = 3;   // fragment prefetch distance, in iterations
 template <int B, int E, class F>
 __device__ __forceinline__ void pg_static_for(F&& f) {
   if constexpr (B < E) {
@@ -358,8 +340,8 @@ __device__ __forceinline__ void pg_store(Rsrc r, f32x4 v, int voff, int soff) {
 }
 
 template <int KC, int NC, bool ACC>
-__global__ __launch_bounds__(256, PNTF_PANEL_WPS) void panel_gemm_kernel(PanelArgs g) {
-  constexpr int QK = KC / 8, NG = NC / 128, NQ = NG * QK, PF = PNTF_PANEL_PF, NS = PF + 1;
+__global__ __launch_bounds__(256, 1) void panel_gemm_kernel(PanelArgs g) {
+  constexpr int QK = KC / 8, NG = NC / 128, NQ = NG * QK, PF = PANEL_PF, NS = PF + 1;
   static_assert(NQ % NS == 0, "ring slots must divide the per-tile fragment stream");
   static_assert(QK >= 8, "C prefetch distance");
   const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
@@ -410,11 +392,9 @@ __global__ __launch_bounds__(256, PNTF_PANEL_WPS) void panel_gemm_kernel(PanelAr
       }
       // prefetch PF iterations ahead; past the tile's end the stream wraps to the next tile
       constexpr int pit = (it + PF) % NQ;
-      if constexpr (!(PNTF_PANEL_DIAG & 4)) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-          ring[(it + PF) % NS][t] = pg_load(rp, vp, ((4 * (pit / QK) + t) * QK + pit % QK) * 1024);
-      }
+      for (int t = 0; t < 4; ++t)
+        ring[(it + PF) % NS][t] = pg_load(rp, vp, ((4 * (pit / QK) + t) * QK + pit % QK) * 1024);
       // four independent accumulator chains per k step; the fence keeps the scheduler from
       // regrouping them into back-to-back dependent MFMAs (it orders by load arrival)
 #pragma unroll
@@ -424,10 +404,10 @@ __global__ __launch_bounds__(256, PNTF_PANEL_WPS) void panel_gemm_kernel(PanelAr
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ring[it % NS][t][e], x[q][e], acc[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (G == NG - 1 && !(PNTF_PANEL_DIAG & 1)) {
+      if constexpr (G == NG - 1) {
         if (more) x[q] = pg_load(rn, va, 32 * q);   // x[q] is dead for this tile: next panel
       }
-      if constexpr (q == QK - 1 && !(PNTF_PANEL_DIAG & 2)) {
+      if constexpr (q == QK - 1) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -575,63 +555,28 @@ __global__ __launch_bounds__(256, 1) void panel_lds_kernel(PanelArgs g) {
 // kernels.  The pre-split weight is 1.5x the fp32 bytes, so a workgroup's LDS holds a 64-column
 // group at K = 256 (96 KiB; 128 columns at K = 128) and a 256-column layer has four groups,
 // whose workgroups take block ids 8 apart (one XCD: the panel's later reads hit its L2).
-// C leaves through a per-wave LDS block so that its stores are row-contiguous (1; 0: straight
-// from the MFMA layout, 32 half-filled lines per store)
-#ifndef PNTF_X6_TSTORE
-#define PNTF_X6_TSTORE 1
-#endif
-// Diagnostic variant (1): the A panel arrives row-contiguously (4 lanes per 64-byte row segment,
-// 16 rows per load) and reaches the MFMA layout through a per-wave LDS block two k blocks ahead
-// of its split.  Same-box A/B against the direct loads (0, shipped; one lane per row, 32 cache
-// lines per load): no difference (generator forward 175.1 vs 173.8 TFLOP/s,
-// profiles/r05_x6_gemm.txt), so the half-filled-line loads are not what binds.
-#ifndef PNTF_X6_LSTAGE
-#define PNTF_X6_LSTAGE 0
-#endif
-// 1: reload a panel block's registers in the block that splits them (one k block more lead
-// for the next tile's loads); 0: one block later
-#ifndef PNTF_X6_EARLY
-#define PNTF_X6_EARLY 0
-#endif
-// diagnostics only (tests/diag/gemm_variants.py ablations; wrong results): bit 1 no operand
-// split, 2 no LDS fragment reads in the loop, 4 no next-panel loads, 8 no C stores, 16 every
-// panel load from the first tile (L2-resident), 32 the panel's bytes read row-contiguously
-#ifndef PNTF_X6_ABL
-#define PNTF_X6_ABL 0
-#endif
+// C leaves through a per-wave LDS block so that its stores are row-contiguous (straight from the
+// MFMA layout they would be 32 half-filled lines per store).  Tried: the A panel loaded row-contiguously and
+// staged through LDS into the MFMA layout, against the direct loads kept here (one lane per row,
+// 32 cache lines per load): no difference (generator forward 175.1 vs 173.8 TFLOP/s,
+// profiles/r05_x6_gemm.txt), so the half-filled-line loads are not what binds.  Tried: reloading
+// a panel block's registers one k block earlier, and ablations of the split, the LDS fragment
+// reads, the panel loads and the C stores: profiles/r05_x6_gemm.txt.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// PNTF_X6_DOT = 1: each split stage's residual v - bf16(v) is one v_dot2c_f32_bf16 per
-// element (v + p.lo·(-1) + p.hi·0, exact), not an unpack and a subtract (pntf_common.h)
-#ifndef PNTF_X6_DOT
-#define PNTF_X6_DOT 0
-#endif
-__device__ __forceinline__ f32x2 x6_resid(f32x2 v, bf16x2 p) {
-  // (-1, -0) and (-0, -1) as 32-bit literals: the plain (-1, 0) would be encoded as the inline
-  // constant -1.0, which the hardware does not read as the bf16 pair (-1, 0)
-  const bf16x2 nlo = __builtin_bit_cast(bf16x2, 0x8000bf80u), nhi = __builtin_bit_cast(bf16x2, 0xbf808000u);
-  f32x2 r;
-  r[0] = __builtin_amdgcn_fdot2_f32_bf16(p, nlo, v[0], false);
-  r[1] = __builtin_amdgcn_fdot2_f32_bf16(p, nhi, v[1], false);
-  return r;
-}
-// three-term RNE split of 8 fp32 (k order of the bf16 operand lane: 8 consecutive k)
+// three-term RNE split of 8 fp32 (k order of the bf16 operand lane: 8 consecutive k).  Tried:
+// each stage's residual v - bf16(v) as one v_dot2c_f32_bf16 per element instead of an unpack and
+// a subtract (measured on the wide kernel's same split, profiles/r06_wide_variants.txt).
 __device__ __forceinline__ void x6_split(const f32x4& a, const f32x4& b, bf16x8 (&s)[3]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const f32x2 v = i < 2 ? f32x2{a[2 * i], a[2 * i + 1]} : f32x2{b[2 * i - 4], b[2 * i - 3]};
     const bf16x2 p0 = __builtin_convertvector(v, bf16x2);
-#if PNTF_X6_DOT
-    const f32x2 r1 = x6_resid(v, p0);
-    const bf16x2 p1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = x6_resid(r1, p1);
-#else
     const f32x2 r1 = v - __builtin_convertvector(p0, f32x2);
     const bf16x2 p1 = __builtin_convertvector(r1, bf16x2);
     const f32x2 r2 = r1 - __builtin_convertvector(p1, f32x2);
-#endif
     const bf16x2 p2 = __builtin_convertvector(r2, bf16x2);
     s[0][2 * i] = p0[0]; s[0][2 * i + 1] = p0[1];
     s[1][2 * i] = p1[0]; s[1][2 * i + 1] = p1[1];
@@ -688,13 +633,10 @@ __global__ void x6_pack_kernel(const float* __restrict__ W, int64_t ldb, int tb,
   for (int p = 0; p < 3; ++p) P[((int64_t)(nt * KB + kb) * 3 + p) * 64 + lane] = s[p];
 }
 
-// workgroups (so waves) per CU of the split kernel: 1 holds a 64-column group at K = 256 (128 at
-// K = 128) in 96 KiB of LDS; 2 halves the group (48 KiB) so that two workgroups share a CU and
-// each SIMD runs two waves (<= 256 registers each)
-#ifndef PNTF_X6_WPS
-#define PNTF_X6_WPS 1
-#endif
-constexpr int x6_cg1(int KC) { return (KC == 256 ? 64 : 128) / PNTF_X6_WPS; }
+// one workgroup (so one wave per SIMD) per CU of the split kernel: it holds a 64-column group at
+// K = 256 (128 at K = 128) in 96 KiB of LDS.  Tried: half the group (48 KiB) so that two
+// workgroups share a CU and each SIMD runs two waves of <= 256 registers (profiles/r05_x6_gemm.txt)
+constexpr int x6_cg1(int KC) { return KC == 256 ? 64 : 128; }
 constexpr int x6_cg(int KC, int NC) { return x6_cg1(KC) < NC ? x6_cg1(KC) : NC; }
 
 // V: how the six products accumulate.  0: one accumulator, small products first (x6_mma);
@@ -706,27 +648,18 @@ constexpr int x6_cg(int KC, int NC) { return x6_cg1(KC) < NC ? x6_cg1(KC) : NC; 
 // to the fp32 level or below, at the same speed (tests/diag/x6_train_acc.py, x6_probe.py;
 // profiles/r05_x6_accuracy.txt).
 template <int KC, int NC, bool ACC, int V = 3>
-__global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g) {
+__global__ __launch_bounds__(256, 1) void panel_x6_kernel(PanelArgs g) {
   PNTF_CLOCK_SCOPE;
   constexpr int KB = KC / 16, QK = KC / 8, CG = x6_cg(KC, NC), TG = CG / 32, NG = NC / CG;
   // the LDS-transposed store flushes a block after every odd tile
-  static_assert(!PNTF_X6_TSTORE || TG % 2 == 0, "PNTF_X6_TSTORE needs an even tile count per group");
+  static_assert(TG % 2 == 0, "the transposed store needs an even tile count per group");
   constexpr int FR = TG * KB * 3;   // 1 KiB fragments per group
   static_assert(KB >= 4, "C prefetch distance");
   __shared__ bf16x8 lw[FR * 64];
   __shared__ f32x4 lb[ACC ? CG / 4 : 1];
-#if PNTF_X6_TSTORE
   // per wave: a 32-row x 64-column block of C on its way out (row stride 17 float4: the MFMA
   // layout writes and the row-contiguous reads are both conflict-free)
   __shared__ f32x4 lt[4][32 * 17];
-#endif
-#if PNTF_X6_LSTAGE && PNTF_X6_EARLY
-#error "PNTF_X6_EARLY applies to the direct panel loads"
-#endif
-#if PNTF_X6_LSTAGE
-  // per wave: one k block of the panel (32 rows x 64 bytes, row stride 5 float4: conflict-free)
-  __shared__ f32x4 lst[4][32 * 5];
-#endif
   const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // block b -> (group, workgroup index): the NG workgroups of a set of tiles on one XCD
@@ -754,43 +687,9 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
     return pg_rsrc(base + 32 * t * ld, (rows < 32 ? rows : 32) * ld * 4);
   };
   const int va = (int)((j * g.lda + 8 * h) * 4), vc = (int)((j * g.ldc + 4 * h) * 4);
-#if PNTF_X6_TSTORE
   const int vt = (int)(((lane >> 4) * g.ldc + 4 * (lane & 15)) * 4);
-#endif
-#if PNTF_X6_ABL & 32
-  const int vco = (int)(((lane >> 3) * g.lda) * 4 + 16 * (lane & 7));
-#endif
   const int c0 = CG * grp;
   f32x4 x[QK];
-#if PNTF_X6_LSTAGE
-  // raw panel registers: x[2b + q] = rows 16q + (lane >> 2), bytes 64b + 16 (lane & 3) ..
-  // of the tile (k block b), staged through lst into the MFMA layout two blocks ahead
-  const int vr = (int)(((lane >> 2) * g.lda) * 4 + 16 * (lane & 3));
-  const int sq = __builtin_amdgcn_readfirstlane((int)(64 * g.lda));   // 16 rows, in bytes
-  auto raw = [&](Rsrc r, int b, int q) { return pg_load(r, vr, 64 * b + q * sq); };
-  auto stage = [&](int b, f32x4& y0, f32x4& y1) {
-    lst[w][(lane >> 2) * 5 + (lane & 3)] = x[2 * b];
-    lst[w][(16 + (lane >> 2)) * 5 + (lane & 3)] = x[2 * b + 1];
-    asm volatile("" ::: "memory");     // (compiler order; LDS itself is in order per wave)
-    y0 = lst[w][j * 5 + 2 * h];
-    y1 = lst[w][j * 5 + 2 * h + 1];
-  };
-  auto tile_win = [&](int64_t t) { return win(g.A, g.lda, t < ntiles ? t : tile); };
-  f32x4 y[2];
-  bf16x8 s[3];
-  {
-    const Rsrc ra = win(g.A, g.lda, tile);
-#pragma unroll
-    for (int q = 0; q < QK; ++q) x[q] = raw(ra, q >> 1, q & 1);
-    stage(0, y[0], y[1]);
-    x6_split(y[0], y[1], s);
-    stage(1, y[0], y[1]);
-    // blocks 0 and 1 of the next tile: staged at this tile's blocks KB - 2, KB - 1
-    const Rsrc rn = tile_win(tile + stride);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] = raw(rn, q >> 1, q & 1);
-  }
-#else
   {
     const Rsrc ra = win(g.A, g.lda, tile);
 #pragma unroll
@@ -800,15 +699,6 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
   // block's MFMAs (software pipeline, wrapping into the next tile's first block)
   bf16x8 s[3];
   x6_split(x[0], x[1], s);
-#if PNTF_X6_EARLY
-  {   // block 0 of the next tile (split at this tile's last block)
-    const int64_t t1 = tile + stride;
-    const Rsrc r1 = win(g.A, g.lda, t1 < ntiles ? t1 : tile);
-    x[0] = pg_load(r1, va, 0);
-    x[1] = pg_load(r1, va, 16);
-  }
-#endif
-#endif
   const bf16x8* lf = lw + lane;
   bf16x8 fr[2][TG][3];
 #pragma unroll
@@ -818,11 +708,7 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
   for (;;) {
     const int64_t next = tile + stride;
     const bool more = next < ntiles;
-#if PNTF_X6_ABL & 16
-    const Rsrc rn = win(g.A, g.lda, 0);   // every panel load hits the first tile (L2)
-#else
     const Rsrc rn = win(g.A, g.lda, more ? next : tile);
-#endif
     const Rsrc rc = win(g.C, g.ldc, tile), rci = win(g.Cin, g.ldc, tile);
     f32x16 acc[TG], accl[V == 1 || V == 3 ? TG : 1], accm[V == 3 ? TG : 1];
     f32x4 cb[TG][4];
@@ -852,47 +738,14 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
       }
       // next k block's fragments (past the tile's end: the next tile's first ones)
       constexpr int kn = (kb + 1) % KB;
-#if !(PNTF_X6_ABL & 2)
 #pragma unroll
       for (int t = 0; t < TG; ++t)
 #pragma unroll
         for (int p = 0; p < 3; ++p) fr[cur ^ 1][t][p] = lf[((t * KB + kn) * 3 + p) * 64];
-#else
-#pragma unroll
-      for (int t = 0; t < TG; ++t)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) fr[cur ^ 1][t][p] = fr[cur][t][p];
-#endif
       // next block's terms (past the tile's end: the next panel's first block, loaded at
       // this tile's block 0)
       bf16x8 sn[3];
-#if PNTF_X6_LSTAGE
-      // stage block kb + 2 (the next tile's 0 / 1 past the end), reload its raw registers
-      // with the tile one further, and split block kb + 1 (staged one block ago)
-      f32x4 yn[2];
-      {
-        constexpr int b2 = (kb + 2) % KB;
-        stage(b2, yn[0], yn[1]);
-        const Rsrc rr = kb + 2 < KB ? rn : tile_win(tile + 2 * stride);
-        x[2 * b2] = raw(rr, b2, 0);
-        x[2 * b2 + 1] = raw(rr, b2, 1);
-      }
-      x6_split(y[0], y[1], sn);
-#elif !(PNTF_X6_ABL & 1)
       x6_split(x[2 * kn], x[2 * kn + 1], sn);
-#if PNTF_X6_EARLY
-      {   // x[2kn], x[2kn + 1] are dead now: the next tile's block kn (the one after for kn = 0)
-        const int64_t t2 = tile + 2 * stride;
-        const Rsrc rr = kn != 0 ? rn : win(g.A, g.lda, t2 < ntiles ? t2 : tile);
-        x[2 * kn] = pg_load(rr, va, 64 * kn);
-        x[2 * kn + 1] = pg_load(rr, va, 64 * kn + 16);
-      }
-#endif
-#else
-      sn[0] = __builtin_bit_cast(bf16x8, x[2 * kn]);
-      sn[1] = __builtin_bit_cast(bf16x8, x[2 * kn + 1]);
-      sn[2] = sn[0];
-#endif
 #pragma unroll
       for (int t = 0; t < TG; ++t) {
         if constexpr (V == 1) {
@@ -908,18 +761,8 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
       }
       // x[2kb], x[2kb + 1] were split one block ago: reload them with the next panel's (the
       // last tile reloads its own: no branch in the MFMA stream)
-#if PNTF_X6_LSTAGE
-      y[0] = yn[0];
-      y[1] = yn[1];
-#elif PNTF_X6_ABL & 32
-      // (the same bytes per tile read row-contiguously: 8 lanes per 128-byte line, 8 rows per
-      // instruction; wrong operands)
-      x[2 * kb] = pg_load(rn, vco, 4096 * (kb & 3) + 128 * (kb >> 2));
-      x[2 * kb + 1] = pg_load(rn, vco, 4096 * (kb & 3) + 128 * (kb >> 2) + 64);
-#elif !(PNTF_X6_ABL & 4) && !PNTF_X6_EARLY
       x[2 * kb] = pg_load(rn, va, 64 * kb);
       x[2 * kb + 1] = pg_load(rn, va, 64 * kb + 16);
-#endif
 #pragma unroll
       for (int p = 0; p < 3; ++p) s[p] = sn[p];
       if constexpr (kb == KB - 1) {
@@ -939,16 +782,9 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
               if (brow) v += lb[8 * t + 2 * R + h];
               v += cb[t][R];
             }
-#if PNTF_X6_TSTORE
             // lane (j, h) holds row j's columns 32t + 8R + 4h .. +3 of the 64-column block
             lt[w][j * 17 + 8 * (t & 1) + 2 * R + h] = v;
-#elif !(PNTF_X6_ABL & 8)
-            pg_store(rc, v, vc, (c0 + 32 * t + 8 * R) * 4);
-#else
-            if (v[0] == 1.2345f) pg_store(rc, v, vc, (c0 + 32 * t + 8 * R) * 4);
-#endif
           }
-#if PNTF_X6_TSTORE
           if (t & 1) {
             // the block's rows go out row-contiguously: 16 lanes x 16 B per 256-byte row,
             // four rows per store (8 cache lines instead of 32 half-filled ones).  LDS is in
@@ -957,14 +793,9 @@ __global__ __launch_bounds__(256, PNTF_X6_WPS) void panel_x6_kernel(PanelArgs g)
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
               const f32x4 v = lt[w][(4 * i + (lane >> 4)) * 17 + (lane & 15)];
-#if !(PNTF_X6_ABL & 8)
               pg_store(rc, v, vt, (4 * i * (int)g.ldc + c0 + 32 * (t - 1)) * 4);
-#else
-              if (v[0] == 1.2345f) pg_store(rc, v, vt, (4 * i * (int)g.ldc + c0 + 32 * (t - 1)) * 4);
-#endif
             }
           }
-#endif
         }
       }
       // keep each block's loads where they are issued (the scheduler otherwise sinks the next
@@ -1442,12 +1273,10 @@ struct BwdArgs {
   int R, ndir, nl;
 };
 
-#ifndef PNTF_BWD_EARLY
-#define PNTF_BWD_EARLY (QK / 2)
-#endif
 template <int KC, int NC>
 __global__ __launch_bounds__(256, 1) void panel_bwd_coop_kernel(BwdArgs g) {
   constexpr int QK = KC / 8, NG = NC / 128, FR = 4 * QK;
+  constexpr int EARLY = QK / 2;   // the iteration that loads the plane's res / y tiles
   __shared__ f32x4 lw[FR * 64];
   const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1522,7 +1351,7 @@ __global__ __launch_bounds__(256, 1) void panel_bwd_coop_kernel(BwdArgs g) {
             for (int Q = 0; Q < 4; ++Q) s[Q] = pg_load(ry0, vc, (c0 + 8 * Q) * 4);
           }
         }
-        if constexpr (q == PNTF_BWD_EARLY) {   // HBM planes: half a plane of lead or more
+        if constexpr (q == EARLY) {   // HBM planes: half a plane of lead or more
 #pragma unroll
           for (int Q = 0; Q < 4; ++Q) {
             if (has_res) cb[Q] = pg_load(rr, vc, (c0 + 8 * Q) * 4);
@@ -2063,21 +1892,15 @@ int num_cus() {
 }
 
 // Split-K factor: enough workgroups for 2 per CU, chunks of at least 512 rows of K.
-// Tile width: 128 columns.  256 (the A panel read once per row tile, PNTF_GEMM_WIDE=1) halves
-// the occupancy and measured 10-20 % slower on the training shapes (tests/diag/gemm_variants.py).
-#ifndef PNTF_GEMM_WIDE
-#define PNTF_GEMM_WIDE 0
-#endif
-int tile_n(int64_t M, int64_t N) {
-  return PNTF_GEMM_WIDE && N % 256 == 0 && (M + BM - 1) / BM >= 2 * (int64_t)num_cus() ? 256 : 128;
-}
-
+// Tile width: 128 columns.  Tried: 256 (the A panel read once per row tile) halves the
+// occupancy and measured 10-20 % slower on the training shapes (tests/diag/gemm_variants.py).
 int64_t splits_for(int64_t M, int64_t N, int64_t K) {
-  const int64_t tiles = ((M + BM - 1) / BM) * (N / tile_n(M, N));
+  constexpr int64_t max_splits = 512;
+  const int64_t tiles = ((M + BM - 1) / BM) * (N / BN);
   int64_t s = (2 * (int64_t)num_cus() + tiles - 1) / tiles;
   const int64_t kmax = (K + 511) / 512;
   if (s > kmax) s = kmax;
-  if (s > PNTF_GEMM_SPLITS) s = PNTF_GEMM_SPLITS;
+  if (s > max_splits) s = max_splits;
   // whole waves of workgroups: 273 splits of a 128x128 gradient put a second workgroup on 17
   // CUs and doubled the kernel's time; round the grid down to a multiple of the CU count
   const int64_t cus = num_cus();
@@ -2145,11 +1968,218 @@ int64_t wgrad_splits(int64_t M, int64_t N, int64_t K) {
   return s < 1 ? 1 : s;
 }
 
+// ---------------------------------------------------------------------------------------
+// Host launch helpers (file-local).
+namespace {
+
+// status of the launches since the last call, with the message under the entry point's name
+int launch_status(const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return PNTF_OK;
+  snprintf(g_err, sizeof(g_err), "%s: %s", who, hipGetErrorString(e));
+  return PNTF_ERR_HIP;
+}
+
+// a kernel that takes one argument struct
+template <class Args>
+void launch(void (*kernel)(Args), dim3 grid, unsigned block, hipStream_t stream, const Args& a) {
+  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, stream, a);
+}
+
+// f(KC, NC) with the shape as compile-time constants, K, N ∈ {128, 256} (panel_shape)
+template <class F>
+void for_kn(int64_t K, int64_t N, F&& f) {
+  constexpr std::integral_constant<int, 128> c128{};
+  constexpr std::integral_constant<int, 256> c256{};
+  if (K == 128 && N == 128) f(c128, c128);
+  else if (K == 128) f(c128, c256);
+  else if (N == 128) f(c256, c128);
+  else f(c256, c256);
+}
+
+// f(T) with the weight gradient's tile count, 1, 2 or 4, as a compile-time constant
+template <class F>
+void for_tiles(int T, F&& f) {
+  if (T == 1) f(std::integral_constant<int, 1>{});
+  else if (T == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+// Workgroups per column group of a persistent kernel: at most per_cu·CUs / groups of them, and
+// with pad8 a multiple of 8, so that the group workgroups of a set of tiles share an XCD (idle
+// workgroups past the last tile return at once).
+int64_t group_wgs(int64_t wgs, int64_t groups, bool pad8, int per_cu) {
+  const int64_t cap = per_cu * num_cus() / groups;
+  const int64_t n = wgs < cap ? wgs : cap;
+  return pad8 ? (n + 7) / 8 * 8 : n;
+}
+
+// a pack kernel over nf lanes (64 per fragment): op(B) into `work` in fragment order
+template <class P>
+void launch_pack(void (*kernel)(const float*, int64_t, int, int, int, P*), int64_t nf,
+                 const float* W, int64_t ldb, int tb, int64_t K, int64_t N, float* work,
+                 hipStream_t stream) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W, ldb, tb,
+                     (int)K, (int)N, reinterpret_cast<P*>(work));
+}
+
+// C = beta·C + the sum of the s partial (M x N) matrices in work (gemm_reduce1 / 2)
+void launch_reduce(float* work, int64_t s, int64_t M, int64_t N, float* C, int64_t ldc, float beta,
+                   hipStream_t stream) {
+  const int64_t n = M * N;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(gemm_reduce1_kernel, dim3(nb, (unsigned)((s + RG - 1) / RG)), dim3(256), 0,
+                     stream, work, (int)s, n);
+  hipLaunchKernelGGL(gemm_reduce2_kernel, dim3(nb), dim3(256), 0, stream, work, (int)s, M, N, C,
+                     ldc, beta);
+}
+
+// the plane layouts of the Loss / value tapes, which the fused Linear kernels take
+bool loss_tape_planes(int ndir, int nl) {
+  return (nl == 0 && ndir == 0) || (nl == 1 && (ndir == 3 || ndir == 6)) ||
+         (nl == 2 && (ndir == 6 || ndir == 12));
+}
+
+// The panel GEMMs' conditions (C = A·op(B) (+ Cin) on the register-panel / LDS-panel kernels)
+bool panel_path(int ta, int64_t N, int64_t K, int64_t lda, int64_t ldc, float beta, const float* A,
+                const float* C, const float* work, size_t work_floats) {
+  return !ta && (beta == 0.f || beta == 1.f) && panel_shape(N, K) && panel_mode() != 0 &&
+         lda == K && ldc == N && work && work_floats >= panel_pack_floats(N, K) &&
+         ((uintptr_t)A & 15) == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)work & 15) == 0;
+}
+
+// pntf_tt_gemm with the LDS panel kernels' epilogue operands: Cin != C (and a bias) only on the
+// LDS panel path (the caller checks panel_path and panel_mode): C = A·op(B) (+ bias on rows <
+// brows) + Cin
+int tt_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+            const float* B, int64_t ldb, float* C, int64_t ldc, float beta, float* work,
+            size_t work_floats, hipStream_t stream, const float* Cin, const float* bias,
+            int64_t brows) {
+  if (M < 0 || N < 0 || K < 0 || N % BN != 0) {
+    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: need M, K >= 0 and N a multiple of %d", BN);
+    return PNTF_ERR_ARG;
+  }
+  if (M == 0 || N == 0) return PNTF_OK;
+  if (!A || !B || !C) {
+    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: null pointer");
+    return PNTF_ERR_ARG;
+  }
+  const int pm = panel_mode();
+  const bool acc = beta != 0.f;
+  if (panel_path(ta, N, K, lda, ldc, beta, A, C, work, work_floats)) {
+    const PanelArgs p{A, reinterpret_cast<const f32x4*>(work), C, M, lda, ldc, Cin, bias, brows};
+    const int64_t wgs = ((M + 31) / 32 + 3) / 4;   // four waves, a 32-row tile each
+    // modes 4 / 5 (diagnostics): the split kernel for the forward (tb) / input-gradient (!tb)
+    // GEMMs only; 6 / 7: its accumulation variants V = 0 / 1
+    const bool x6 = pm == 3 || pm == 6 || pm == 7 || (pm == 4 && tb) || (pm == 5 && !tb);
+    if (pm == 8) {
+      // the 16 x 16 x 32 split-bf16 panel kernel, eight waves (16-row tiles) per workgroup
+      launch_pack(x6s_pack_kernel, (N / 16) * (K / 32) * 64, B, ldb, tb, K, N, work, stream);
+      const int64_t ng = N / X6S_CG;
+      const dim3 grid((unsigned)(group_wgs(((M + 15) / 16 + 7) / 8, ng, ng > 1, 1) * ng));
+      for_kn(K, N, [&](auto kc, auto nc) {
+        constexpr int KC = decltype(kc)::value, NC = decltype(nc)::value;
+        launch(acc ? panel_x6s_kernel<KC, NC, true> : panel_x6s_kernel<KC, NC, false>, grid, 512,
+               stream, p);
+      });
+    } else if (x6) {
+      launch_pack(x6_pack_kernel, (N / 32) * (K / 16) * 64, B, ldb, tb, K, N, work, stream);
+      // one workgroup per CU (96 KiB of LDS); per group at most CUs / NG of them, a multiple of
+      // 8 with several groups so that a tile's group workgroups share an XCD
+      const int64_t cg = x6_cg1((int)K), ng = N / cg > 1 ? N / cg : 1;
+      const dim3 grid((unsigned)(group_wgs(wgs, ng, ng > 1, 1) * ng));
+      for_kn(K, N, [&](auto kc, auto nc) {
+        constexpr int KC = decltype(kc)::value, NC = decltype(nc)::value;
+        launch(pm == 6   ? (acc ? panel_x6_kernel<KC, NC, true, 0> : panel_x6_kernel<KC, NC, false, 0>)
+               : pm == 7 ? (acc ? panel_x6_kernel<KC, NC, true, 1> : panel_x6_kernel<KC, NC, false, 1>)
+                         : (acc ? panel_x6_kernel<KC, NC, true> : panel_x6_kernel<KC, NC, false>),
+               grid, 256, stream, p);
+      });
+    } else if (pm >= 2) {
+      launch_pack(panel_pack_kernel, (N / 32) * (K / 8) * 64, B, ldb, tb, K, N, work, stream);
+      // one workgroup per CU (128 KiB of LDS at K = 256); per group at most CUs / NG of them,
+      // a multiple of 8 so that a tile's two group workgroups share an XCD (N = 256)
+      // (K = 128 without C: 64 KiB of LDS and ≤ 256 registers, so two per CU)
+      const int64_t ng = N / 128;
+      const dim3 grid((unsigned)(group_wgs(wgs, ng, ng == 2, K == 128 && !acc ? 2 : 1) * ng));
+      for_kn(K, N, [&](auto kc, auto nc) {
+        constexpr int KC = decltype(kc)::value, NC = decltype(nc)::value;
+        launch(acc ? panel_lds_kernel<KC, NC, true> : panel_lds_kernel<KC, NC, false>, grid, 256,
+               stream, p);
+      });
+    } else {
+      launch_pack(panel_pack_kernel, (N / 32) * (K / 8) * 64, B, ldb, tb, K, N, work, stream);
+      const dim3 grid((unsigned)group_wgs(wgs, 1, false, 1));   // one workgroup per CU, no groups
+      for_kn(K, N, [&](auto kc, auto nc) {
+        constexpr int KC = decltype(kc)::value, NC = decltype(nc)::value;
+        launch(acc ? panel_gemm_kernel<KC, NC, true> : panel_gemm_kernel<KC, NC, false>, grid, 256,
+               stream, p);
+      });
+    }
+    return launch_status("pntf_tt_gemm");
+  }
+  if (ta && !tb && beta == 0.f && K > 0 && wgrad_shape(M, N) && wgrad_enabled() && lda == M &&
+      ldb == N && work && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
+      ((uintptr_t)work & 15) == 0) {
+    // rows per split: a multiple of 128 (4 waves x two 16-row chunks); the buffer offsets are
+    // 32-bit, so a split must stay below 2 GiB of either operand
+    const int64_t s0 = wgrad_splits(M, N, K);
+    int64_t rps = ((K + s0 - 1) / s0 + 127) / 128 * 128;
+    int64_t s = (K + rps - 1) / rps;
+    // XCD-aware map: pad the split count to a multiple of 8 (empty splits write zeros)
+    const bool xcd = (M / 128) * (N / 128) > 1 && s >= 8;
+    if (xcd) s = (s + 7) / 8 * 8;
+    if (rps * (M > N ? M : N) * 4 < ((int64_t)1 << 31) - ((int64_t)1 << 20) &&
+        work_floats >= (size_t)(s * M * N)) {
+      const int T = (int)((M / 128) * (N / 128));
+      const WgradArgs wa{A, B, work, K, rps, (int)M, (int)N, (int)xcd};
+      const dim3 grid((unsigned)(s * T));
+      for_tiles(T, [&](auto t) {
+        constexpr int TC = decltype(t)::value;
+        launch(wgrad_mode() == 2      ? wgrad_x6_kernel<TC>
+               : wgrad_ring(T) == 2 ? wgrad_kernel<TC, 2>
+                                    : wgrad_kernel<TC, 1>,
+               grid, 256, stream, wa);
+      });
+      launch_reduce(work, s, M, N, C, ldc, beta, stream);
+      return launch_status("pntf_tt_gemm");
+    }
+  }
+  // the LDS-tiled kernel puts the row tiles on grid.y (HIP limit 65535): M above
+  // 65535 * 128 ≈ 8.4M rows cannot launch there (the panel path above has no such limit)
+  if ((M + BM - 1) / BM > 65535) {
+    snprintf(g_err, sizeof(g_err),
+             "pntf_tt_gemm: M = %lld rows exceeds the LDS-tiled kernel's grid (65535 x %d); "
+             "use the panel path (ta = 0, K, N in {128, 256}, beta 0 or 1, aligned operands)",
+             (long long)M, BM);
+    return PNTF_ERR_ARG;
+  }
+  const int64_t s = K > 0 ? splits_for(M, N, K) : 1;
+  if (s > 1 && (!work || work_floats < (size_t)(s * M * N))) {
+    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: work buffer too small");
+    return PNTF_ERR_WORKSPACE;
+  }
+  GemmArgs g{A, B, C, work, M, N, K, lda, ldb, ldc, 0, beta};
+  g.kper = ((K + s - 1) / s + BK - 1) / BK * BK;
+  if (g.kper < BK) g.kper = BK;
+  const dim3 grid((unsigned)(N / BN), (unsigned)((M + BM - 1) / BM), (unsigned)s);
+  launch(ta ? (tb ? gemm_kernel<true, true> : gemm_kernel<true, false>)
+            : (tb ? gemm_kernel<false, true> : gemm_kernel<false, false>),
+         grid, 256, stream, g);
+  if (s > 1) launch_reduce(work, s, M, N, C, ldc, beta, stream);
+  return launch_status("pntf_tt_gemm");
+}
+
+}  // namespace
+
 }  // namespace pntf_gemm
 
 using namespace pntf_gemm;
 
 extern "C" {
+
+int pntf_tt_act_fwd_biased(int ndir, int nl, const float* y, float* h, int64_t m, int w,
+                           hipStream_t stream);
 
 size_t pntf_tt_gemm_work_floats(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
@@ -2163,23 +2193,11 @@ size_t pntf_tt_gemm_work_floats(int64_t M, int64_t N, int64_t K) {
   return big > wgrad ? big : wgrad;
 }
 
-// The panel GEMMs' conditions (C = A·op(B) (+ Cin) on the register-panel / LDS-panel kernels)
-static bool panel_path(int ta, int64_t N, int64_t K, int64_t lda, int64_t ldc, float beta,
-                       const float* A, const float* C, const float* work, size_t work_floats) {
-  return !ta && (beta == 0.f || beta == 1.f) && panel_shape(N, K) && panel_mode() != 0 &&
-         lda == K && ldc == N && work && work_floats >= panel_pack_floats(N, K) &&
-         ((uintptr_t)A & 15) == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)work & 15) == 0;
-}
-
-static int tt_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
-                   const float* B, int64_t ldb, float* C, int64_t ldc, float beta, float* work,
-                   size_t work_floats, hipStream_t stream, const float* Cin,
-                   const float* bias = nullptr, int64_t brows = 0);
-
 int pntf_tt_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                  const float* B, int64_t ldb, float* C, int64_t ldc, float beta, float* work,
                  size_t work_floats, hipStream_t stream) {
-  return tt_gemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, beta, work, work_floats, stream, C);
+  return tt_gemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, beta, work, work_floats, stream, C,
+                 nullptr, 0);
 }
 
 int pntf_tt_set_panel_mode(int mode) {
@@ -2200,230 +2218,9 @@ int pntf_tt_set_bwd_mode(int mode) {
   return prev;
 }
 
-extern "C" int pntf_tt_act_fwd_biased(int ndir, int nl, const float* y, float* h, int64_t m,
-                                      int w, hipStream_t stream);
-
-// Cin != C (and a bias) only on the LDS panel path (the caller checks panel_path and
-// panel_mode): C = A·op(B) (+ bias on rows < brows) + Cin
-static int tt_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
-                   const float* B, int64_t ldb, float* C, int64_t ldc, float beta, float* work,
-                   size_t work_floats, hipStream_t stream, const float* Cin, const float* bias,
-                   int64_t brows) {
-  if (M < 0 || N < 0 || K < 0 || N % BN != 0) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: need M, K >= 0 and N a multiple of %d", BN);
-    return PNTF_ERR_ARG;
-  }
-  if (M == 0 || N == 0) return PNTF_OK;
-  if (!A || !B || !C) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: null pointer");
-    return PNTF_ERR_ARG;
-  }
-  const int pm = panel_mode();
-  if (panel_path(ta, N, K, lda, ldc, beta, A, C, work, work_floats) && pm == 8) {
-    // the 16 x 16 x 32 split-bf16 panel kernel, eight waves per workgroup
-    const int64_t nf = (N / 16) * (K / 32) * 64;
-    hipLaunchKernelGGL(x6s_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream,
-                       B, ldb, tb, (int)K, (int)N, reinterpret_cast<bf16x8*>(work));
-    PanelArgs p{A, reinterpret_cast<const f32x4*>(work), C, M, lda, ldc, Cin, bias, brows};
-    const int64_t tiles = (M + 15) / 16, wgs = (tiles + 7) / 8;
-    const int64_t ng = N / X6S_CG, cap = num_cus() / ng;
-    int64_t nwg = wgs < cap ? wgs : cap;
-    if (ng > 1) nwg = (nwg + 7) / 8 * 8;
-    const dim3 grid((unsigned)(nwg * ng));
-#define PNTF_PANEL(KC, NC)                                                                      \
-  if (beta != 0.f) hipLaunchKernelGGL((panel_x6s_kernel<KC, NC, true>), grid, dim3(512), 0,      \
-                                      stream, p);                                               \
-  else hipLaunchKernelGGL((panel_x6s_kernel<KC, NC, false>), grid, dim3(512), 0, stream, p);
-    if (K == 128 && N == 128) { PNTF_PANEL(128, 128) }
-    else if (K == 128) { PNTF_PANEL(128, 256) }
-    else if (N == 128) { PNTF_PANEL(256, 128) }
-    else { PNTF_PANEL(256, 256) }
-#undef PNTF_PANEL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-      return PNTF_ERR_HIP;
-    }
-    return PNTF_OK;
-  }
-  // modes 4 / 5 (diagnostics): the split kernel for the forward (tb) / input-gradient (!tb)
-  // GEMMs only; 6 / 7: its accumulation variants V = 0 / 1
-  const bool x6 = pm == 3 || pm == 6 || pm == 7 || (pm == 4 && tb) || (pm == 5 && !tb);
-  if (panel_path(ta, N, K, lda, ldc, beta, A, C, work, work_floats) && x6) {
-    const int64_t nf = (N / 32) * (K / 16) * 64;
-    hipLaunchKernelGGL(x6_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream,
-                       B, ldb, tb, (int)K, (int)N, reinterpret_cast<bf16x8*>(work));
-    PanelArgs p{A, reinterpret_cast<const f32x4*>(work), C, M, lda, ldc, Cin, bias, brows};
-    // one workgroup per CU (96 KiB of LDS); per group at most CUs / NG of them, a multiple of
-    // 8 with several groups so that a tile's group workgroups share an XCD
-    const int64_t tiles = (M + 31) / 32, wgs = (tiles + 3) / 4;
-    const int64_t cg = K == 256 ? x6_cg1(256) : x6_cg1(128);
-    const int64_t ng = N / cg > 1 ? N / cg : 1;
-    const int64_t cap = PNTF_X6_WPS * num_cus() / ng;
-    int64_t nwg = wgs < cap ? wgs : cap;
-    if (ng > 1) nwg = (nwg + 7) / 8 * 8;
-    const dim3 grid((unsigned)(nwg * ng));
-#define PNTF_PANEL(KC, NC)                                                                      \
-  if (pm == 6) {                                                                                \
-    if (beta != 0.f) hipLaunchKernelGGL((panel_x6_kernel<KC, NC, true, 0>), grid, dim3(256), 0,  \
-                                        stream, p);                                             \
-    else hipLaunchKernelGGL((panel_x6_kernel<KC, NC, false, 0>), grid, dim3(256), 0, stream, p); \
-  } else if (pm == 7) {                                                                         \
-    if (beta != 0.f) hipLaunchKernelGGL((panel_x6_kernel<KC, NC, true, 1>), grid, dim3(256), 0,  \
-                                        stream, p);                                             \
-    else hipLaunchKernelGGL((panel_x6_kernel<KC, NC, false, 1>), grid, dim3(256), 0, stream, p); \
-  } else if (beta != 0.f) hipLaunchKernelGGL((panel_x6_kernel<KC, NC, true>), grid, dim3(256), 0, \
-                                             stream, p);                                        \
-  else hipLaunchKernelGGL((panel_x6_kernel<KC, NC, false>), grid, dim3(256), 0, stream, p);
-    if (K == 128 && N == 128) { PNTF_PANEL(128, 128) }
-    else if (K == 128) { PNTF_PANEL(128, 256) }
-    else if (N == 128) { PNTF_PANEL(256, 128) }
-    else { PNTF_PANEL(256, 256) }
-#undef PNTF_PANEL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-      return PNTF_ERR_HIP;
-    }
-    return PNTF_OK;
-  }
-  if (panel_path(ta, N, K, lda, ldc, beta, A, C, work, work_floats)) {
-    const int64_t nf = (N / 32) * (K / 8) * 64;
-    hipLaunchKernelGGL(panel_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0,
-                       stream, B, ldb, tb, (int)K, (int)N, reinterpret_cast<f32x4*>(work));
-    PanelArgs p{A, reinterpret_cast<const f32x4*>(work), C, M, lda, ldc, Cin, bias, brows};
-    const int64_t tiles = (M + 31) / 32, wgs = (tiles + 3) / 4;
-    if (panel_mode() >= 2) {
-      // one workgroup per CU (128 KiB of LDS at K = 256); per group at most CUs / NG of them
-      // a multiple of 8 so that a tile's two group workgroups share an XCD (N = 256)
-      // (K = 128 without C: 64 KiB of LDS and ≤ 256 registers, so two per CU)
-      const int64_t ng = N / 128, cap = (K == 128 && beta == 0.f ? 2 : 1) * num_cus() / ng;
-      int64_t nwg = wgs < cap ? wgs : cap;
-      if (ng == 2) nwg = (nwg + 7) / 8 * 8;
-      const dim3 grid((unsigned)(nwg * ng));
-#define PNTF_PANEL(KC, NC)                                                                      \
-  if (beta != 0.f) hipLaunchKernelGGL((panel_lds_kernel<KC, NC, true>), grid, dim3(256), 0,      \
-                                      stream, p);                                               \
-  else hipLaunchKernelGGL((panel_lds_kernel<KC, NC, false>), grid, dim3(256), 0, stream, p);
-      if (K == 128 && N == 128) { PNTF_PANEL(128, 128) }
-      else if (K == 128) { PNTF_PANEL(128, 256) }
-      else if (N == 128) { PNTF_PANEL(256, 128) }
-      else { PNTF_PANEL(256, 256) }
-#undef PNTF_PANEL
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-        return PNTF_ERR_HIP;
-      }
-      return PNTF_OK;
-    }
-    const int64_t slots = (int64_t)PNTF_PANEL_WPS * num_cus();
-    const unsigned grid = (unsigned)(wgs < slots ? wgs : slots);
-#define PNTF_PANEL(KC, NC)                                                                     \
-  if (beta != 0.f) hipLaunchKernelGGL((panel_gemm_kernel<KC, NC, true>), dim3(grid), dim3(256), \
-                                      0, stream, p);                                           \
-  else hipLaunchKernelGGL((panel_gemm_kernel<KC, NC, false>), dim3(grid), dim3(256), 0, stream, p);
-    if (K == 128 && N == 128) { PNTF_PANEL(128, 128) }
-    else if (K == 128) { PNTF_PANEL(128, 256) }
-    else if (N == 128) { PNTF_PANEL(256, 128) }
-    else { PNTF_PANEL(256, 256) }
-#undef PNTF_PANEL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-      return PNTF_ERR_HIP;
-    }
-    return PNTF_OK;
-  }
-  if (ta && !tb && beta == 0.f && K > 0 && wgrad_shape(M, N) && wgrad_enabled() && lda == M &&
-      ldb == N && work && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-      ((uintptr_t)work & 15) == 0) {
-    // rows per split: a multiple of 128 (4 waves x two 16-row chunks); the buffer offsets are
-    // 32-bit, so a split must stay below 2 GiB of either operand
-    const int64_t s0 = wgrad_splits(M, N, K);
-    int64_t rps = ((K + s0 - 1) / s0 + 127) / 128 * 128;
-    int64_t s = (K + rps - 1) / rps;
-    // XCD-aware map: pad the split count to a multiple of 8 (empty splits write zeros)
-    const bool xcd = (M / 128) * (N / 128) > 1 && s >= 8;
-    if (xcd) s = (s + 7) / 8 * 8;
-    if (rps * (M > N ? M : N) * 4 < ((int64_t)1 << 31) - ((int64_t)1 << 20) &&
-        work_floats >= (size_t)(s * M * N)) {
-      const int T = (int)((M / 128) * (N / 128));
-      WgradArgs wa{A, B, work, K, rps, (int)M, (int)N, (int)xcd};
-      const dim3 grid((unsigned)(s * T));
-#define PNTF_WGRAD(NB)                                                                          \
-  if (T == 1) hipLaunchKernelGGL((wgrad_kernel<1, NB>), grid, dim3(256), 0, stream, wa);         \
-  else if (T == 2) hipLaunchKernelGGL((wgrad_kernel<2, NB>), grid, dim3(256), 0, stream, wa);    \
-  else hipLaunchKernelGGL((wgrad_kernel<4, NB>), grid, dim3(256), 0, stream, wa);
-      if (wgrad_mode() == 2) {
-        if (T == 1) hipLaunchKernelGGL((wgrad_x6_kernel<1>), grid, dim3(256), 0, stream, wa);
-        else if (T == 2) hipLaunchKernelGGL((wgrad_x6_kernel<2>), grid, dim3(256), 0, stream, wa);
-        else hipLaunchKernelGGL((wgrad_x6_kernel<4>), grid, dim3(256), 0, stream, wa);
-      } else if (wgrad_ring(T) == 2) { PNTF_WGRAD(2) } else { PNTF_WGRAD(1) }
-#undef PNTF_WGRAD
-      const int64_t n = M * N;
-      const unsigned nb = (unsigned)((n + 255) / 256);
-      hipLaunchKernelGGL(gemm_reduce1_kernel, dim3(nb, (unsigned)((s + RG - 1) / RG)),
-                         dim3(256), 0, stream, work, (int)s, n);
-      hipLaunchKernelGGL(gemm_reduce2_kernel, dim3(nb), dim3(256), 0, stream, work, (int)s, M,
-                         N, C, ldc, beta);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-        return PNTF_ERR_HIP;
-      }
-      return PNTF_OK;
-    }
-  }
-  // the LDS-tiled kernel puts the row tiles on grid.y (HIP limit 65535): M above
-  // 65535 * 128 ≈ 8.4M rows cannot launch there (the panel path above has no such limit)
-  if ((M + BM - 1) / BM > 65535) {
-    snprintf(g_err, sizeof(g_err),
-             "pntf_tt_gemm: M = %lld rows exceeds the LDS-tiled kernel's grid (65535 x %d); "
-             "use the panel path (ta = 0, K, N in {128, 256}, beta 0 or 1, aligned operands)",
-             (long long)M, BM);
-    return PNTF_ERR_ARG;
-  }
-  const int64_t s = K > 0 ? splits_for(M, N, K) : 1;
-  if (s > 1 && (!work || work_floats < (size_t)(s * M * N))) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: work buffer too small");
-    return PNTF_ERR_WORKSPACE;
-  }
-  GemmArgs g{A, B, C, work, M, N, K, lda, ldb, ldc, 0, beta};
-  g.kper = ((K + s - 1) / s + BK - 1) / BK * BK;
-  if (g.kper < BK) g.kper = BK;
-  const int bn = tile_n(M, N);
-  dim3 grid((unsigned)(N / bn), (unsigned)((M + BM - 1) / BM), (unsigned)s), block(256);
-  if (bn == 256) {
-    if (ta && tb) hipLaunchKernelGGL((gemm_kernel<true, true, 256>), grid, block, 0, stream, g);
-    else if (ta) hipLaunchKernelGGL((gemm_kernel<true, false, 256>), grid, block, 0, stream, g);
-    else if (tb) hipLaunchKernelGGL((gemm_kernel<false, true, 256>), grid, block, 0, stream, g);
-    else hipLaunchKernelGGL((gemm_kernel<false, false, 256>), grid, block, 0, stream, g);
-  } else {
-    if (ta && tb) hipLaunchKernelGGL((gemm_kernel<true, true, 128>), grid, block, 0, stream, g);
-    else if (ta) hipLaunchKernelGGL((gemm_kernel<true, false, 128>), grid, block, 0, stream, g);
-    else if (tb) hipLaunchKernelGGL((gemm_kernel<false, true, 128>), grid, block, 0, stream, g);
-    else hipLaunchKernelGGL((gemm_kernel<false, false, 128>), grid, block, 0, stream, g);
-  }
-  if (s > 1) {
-    const int64_t n = M * N;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(gemm_reduce1_kernel, dim3(nb, (unsigned)((s + RG - 1) / RG)), dim3(256),
-                       0, stream, work, (int)s, n);
-    hipLaunchKernelGGL(gemm_reduce2_kernel, dim3(nb), dim3(256), 0, stream, work, (int)s, M, N,
-                       C, ldc, beta);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_gemm: %s", hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
-}
-
 // pntf_train.hip defines the plane check (its with_planes list); this weak copy of the list
 // only serves a standalone build of this file (tests/diag/build_gemm.sh)
-extern "C" __attribute__((weak, visibility("hidden"))) int pntf_tt_planes_ok(int ndir, int nl) {
+__attribute__((weak, visibility("hidden"))) int pntf_tt_planes_ok(int ndir, int nl) {
   const int ok[][2] = {{0, 0}, {3, 1}, {6, 1}, {6, 2}, {12, 2}, {3, 0},
                        {6, 0}, {12, 0}, {3, 3}, {6, 6}, {12, 12}};
   for (const auto& p : ok)
@@ -2436,8 +2233,7 @@ int pntf_tt_linear_act(int ndir, int nl, const float* x, int64_t m, int k, const
                        int schedule, float* work, size_t work_floats, hipStream_t stream) {
   // the fused kernels take the Loss / value tapes' layouts; the first-order and per-direction
   // layouts of the general VJP tape (and act = 2, the out_backgrad quirk) run the GEMM + act pair
-  const bool basic = ((nl == 0 && ndir == 0) || (nl == 1 && (ndir == 3 || ndir == 6)) ||
-                      (nl == 2 && (ndir == 6 || ndir == 12))) && act != 2;
+  const bool basic = loss_tape_planes(ndir, nl) && act != 2;
   const bool planes = pntf_tt_planes_ok(ndir, nl) && act >= 0 && act <= 2;
   const auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   if (!planes || m < 0 || !panel_shape(n, k) || (m > 0 && (!x || !W || !bias || !y || !work ||
@@ -2458,10 +2254,10 @@ int pntf_tt_linear_act(int ndir, int nl, const float* x, int64_t m, int k, const
   // would run two blocks and the rest one.  AUTO takes the fused kernel when the blocks fill
   // their rounds to >= 90 %, otherwise the GEMM (32-row tiles of every plane, balanced) and
   // the act kernel.
-  const int64_t blocks = (m + 31) / 32, wgs = (blocks + 3) / 4;
-  const int64_t ng = n / 128, cap = num_cus() / ng;
-  int64_t nwg = wgs < cap ? wgs : cap;
-  if (ng == 2) nwg = (nwg + 7) / 8 * 8;
+  // As the LDS panel GEMM: one workgroup per CU per column group (a multiple of 8 workgroups
+  // per group for two groups); each wave strides over 32-point blocks.
+  const int64_t blocks = (m + 31) / 32, ng = n / 128;
+  const int64_t nwg = group_wgs((blocks + 3) / 4, ng, ng == 2, 1);
   const int64_t waves = 4 * nwg, rounds = (blocks + waves - 1) / waves;
   // (and only with several rounds per wave: at one round, generator[3] of the reference batch,
   // the fused kernel measured 227 µs against 132 + 56 for the pair, profiles/r04_train_*)
@@ -2484,39 +2280,17 @@ int pntf_tt_linear_act(int ndir, int nl, const float* x, int64_t m, int k, const
     if (st) return st;
     return pntf_tt_act_fwd(ndir, nl, y, h, bias, res, m, n, act, stream);
   }
-  const int64_t nf = (int64_t)(n / 32) * (k / 8) * 64;
-  hipLaunchKernelGGL(panel_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0,
-                     stream, W, (int64_t)k, 1, k, n, reinterpret_cast<f32x4*>(work));
-  ActArgs a{x, reinterpret_cast<const f32x4*>(work), y, h, bias, res, m, R, ndir, nl, act};
-  if (schedule == 3) {
-    // cooperative blocks: one workgroup per CU and column group, each striding over blocks
-    int64_t cw = blocks < cap ? blocks : cap;
-    if (ng == 2) cw = (cw + 7) / 8 * 8;
-    const dim3 cg((unsigned)(cw * ng));
-    if (k == 128 && n == 128) hipLaunchKernelGGL((panel_act_coop_kernel<128, 128>), cg, dim3(256), 0, stream, a);
-    else if (k == 128) hipLaunchKernelGGL((panel_act_coop_kernel<128, 256>), cg, dim3(256), 0, stream, a);
-    else if (n == 128) hipLaunchKernelGGL((panel_act_coop_kernel<256, 128>), cg, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((panel_act_coop_kernel<256, 256>), cg, dim3(256), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "pntf_tt_linear_act: %s", hipGetErrorString(e));
-      return PNTF_ERR_HIP;
-    }
-    return PNTF_OK;
-  }
-  // as the LDS panel GEMM: one workgroup per CU per column group (a multiple of 8 workgroups
-  // per group for two groups); each wave strides over 32-point blocks
-  const dim3 grid((unsigned)(nwg * ng));
-  if (k == 128 && n == 128) hipLaunchKernelGGL((panel_act_kernel<128, 128>), grid, dim3(256), 0, stream, a);
-  else if (k == 128) hipLaunchKernelGGL((panel_act_kernel<128, 256>), grid, dim3(256), 0, stream, a);
-  else if (n == 128) hipLaunchKernelGGL((panel_act_kernel<256, 128>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((panel_act_kernel<256, 256>), grid, dim3(256), 0, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_linear_act: %s", hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
+  launch_pack(panel_pack_kernel, (int64_t)(n / 32) * (k / 8) * 64, W, k, 1, k, n, work, stream);
+  const ActArgs a{x, reinterpret_cast<const f32x4*>(work), y, h, bias, res, m, R, ndir, nl, act};
+  // schedule 3, cooperative blocks: one workgroup per CU and column group, each striding over
+  // blocks; otherwise a wave per block on the grid sized above
+  const bool coop = schedule == 3;
+  const dim3 grid((unsigned)((coop ? group_wgs(blocks, ng, ng == 2, 1) : nwg) * ng));
+  for_kn(k, n, [&](auto kc, auto nc) {
+    constexpr int KC = decltype(kc)::value, NC = decltype(nc)::value;
+    launch(coop ? panel_act_coop_kernel<KC, NC> : panel_act_kernel<KC, NC>, grid, 256, stream, a);
+  });
+  return launch_status("pntf_tt_linear_act");
 }
 
 size_t pntf_tt_linear_bwd_work_floats(int kc, int nc) {
@@ -2528,10 +2302,8 @@ size_t pntf_tt_linear_bwd_work_floats(int kc, int nc) {
 int pntf_tt_linear_bwd(int ndir, int nl, const float* gy, int64_t m, int kc, const float* W,
                        int nc, const float* yprev, const float* res, float* out, float* gbias,
                        float* work, size_t work_floats, hipStream_t stream) {
-  const bool planes = (nl == 0 && ndir == 0) || (nl == 1 && (ndir == 3 || ndir == 6)) ||
-                      (nl == 2 && (ndir == 6 || ndir == 12));
   const auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  if (!planes || m < 0 || !panel_shape(nc, kc) || !gbias ||
+  if (!loss_tape_planes(ndir, nl) || m < 0 || !panel_shape(nc, kc) || !gbias ||
       (m > 0 && (!gy || !W || !yprev || !out || !work)) ||
       work_floats < pntf_tt_linear_bwd_work_floats(kc, nc) || !al(gy) || !al(yprev) ||
       !al(res) || !al(out) || !al(work)) {
@@ -2543,52 +2315,32 @@ int pntf_tt_linear_bwd(int ndir, int nl, const float* gy, int64_t m, int kc, con
     return PNTF_OK;
   }
   const int R = 1 + ndir + nl;
-  if (bwd_mode() == 1) {
-    const int64_t nf = (int64_t)(nc / 32) * (kc / 16) * 64;
-    hipLaunchKernelGGL(x6_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream,
-                       W, (int64_t)nc, 0, kc, nc, reinterpret_cast<bf16x8*>(work));
-    float* partial = work + (size_t)kc * nc * 3 / 2;
+  const bool x6 = bwd_mode() == 1;
+  // the packed weight (three bf16 terms, or fp32), then the bias partials
+  float* partial = work + (x6 ? (size_t)kc * nc * 3 / 2 : (size_t)kc * nc);
+  const BwdArgs a{gy, reinterpret_cast<const f32x4*>(work), yprev, res, out, partial, m, R, ndir, nl};
+  const int64_t blocks = (m + 31) / 32;
+  int64_t cw, ng;   // workgroups per column group, column groups
+  if (x6) {
+    launch_pack(x6_pack_kernel, (int64_t)(nc / 32) * (kc / 16) * 64, W, nc, 0, kc, nc, work, stream);
     // one workgroup per CU (96 KiB of LDS), each on two 32-point blocks at a time; per 64-column
     // group at most CUs / NG of them, a multiple of 8 so a block's group workgroups share an XCD
-    const int64_t pairs = ((m + 31) / 32 + 1) / 2, ng = nc / 64, cap = num_cus() / ng;
-    int64_t cw = pairs < cap ? pairs : cap;
-    cw = (cw + 7) / 8 * 8;
-    BwdArgs a{gy, reinterpret_cast<const f32x4*>(work), yprev, res, out, partial, m, R, ndir, nl};
-    const dim3 cg((unsigned)(cw * ng));
-    if (kc == 128 && nc == 128) hipLaunchKernelGGL((panel_bwd_x6_kernel<128, 128>), cg, dim3(256), 0, stream, a);
-    else if (kc == 128) hipLaunchKernelGGL((panel_bwd_x6_kernel<128, 256>), cg, dim3(256), 0, stream, a);
-    else if (nc == 128) hipLaunchKernelGGL((panel_bwd_x6_kernel<256, 128>), cg, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((panel_bwd_x6_kernel<256, 256>), cg, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(colsum_kernel, dim3((nc + 255) / 256), dim3(256), 0, stream, partial,
-                       (int)(2 * cw), nc, gbias);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "pntf_tt_linear_bwd: %s", hipGetErrorString(e));
-      return PNTF_ERR_HIP;
-    }
-    return PNTF_OK;
+    ng = nc / 64;
+    cw = group_wgs((blocks + 1) / 2, ng, true, 1);
+  } else {
+    launch_pack(panel_pack_kernel, (int64_t)(nc / 32) * (kc / 8) * 64, W, nc, 0, kc, nc, work, stream);
+    ng = nc / 128;
+    cw = group_wgs(blocks, ng, ng == 2, 1);
   }
-  const int64_t nf = (int64_t)(nc / 32) * (kc / 8) * 64;
-  hipLaunchKernelGGL(panel_pack_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0,
-                     stream, W, (int64_t)nc, 0, kc, nc, reinterpret_cast<f32x4*>(work));
-  float* partial = work + (size_t)kc * nc;
-  const int64_t blocks = (m + 31) / 32, ng = nc / 128, cap = num_cus() / ng;
-  int64_t cw = blocks < cap ? blocks : cap;
-  if (ng == 2) cw = (cw + 7) / 8 * 8;
-  BwdArgs a{gy, reinterpret_cast<const f32x4*>(work), yprev, res, out, partial, m, R, ndir, nl};
-  const dim3 cg((unsigned)(cw * ng));
-  if (kc == 128 && nc == 128) hipLaunchKernelGGL((panel_bwd_coop_kernel<128, 128>), cg, dim3(256), 0, stream, a);
-  else if (kc == 128) hipLaunchKernelGGL((panel_bwd_coop_kernel<128, 256>), cg, dim3(256), 0, stream, a);
-  else if (nc == 128) hipLaunchKernelGGL((panel_bwd_coop_kernel<256, 128>), cg, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((panel_bwd_coop_kernel<256, 256>), cg, dim3(256), 0, stream, a);
+  const dim3 grid((unsigned)(cw * ng));
+  for_kn(kc, nc, [&](auto k, auto n) {
+    constexpr int KC = decltype(k)::value, NC = decltype(n)::value;
+    launch(x6 ? panel_bwd_x6_kernel<KC, NC> : panel_bwd_coop_kernel<KC, NC>, grid, 256, stream, a);
+  });
+  // a split-bf16 workgroup writes one row of bias partials per block of its pair
   hipLaunchKernelGGL(colsum_kernel, dim3((nc + 255) / 256), dim3(256), 0, stream, partial,
-                     (int)cw, nc, gbias);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "pntf_tt_linear_bwd: %s", hipGetErrorString(e));
-    return PNTF_ERR_HIP;
-  }
-  return PNTF_OK;
+                     (int)(x6 ? 2 * cw : cw), nc, gbias);
+  return launch_status("pntf_tt_linear_bwd");
 }
 
 const char* pntf_tt_gemm_last_error(void) { return g_err; }

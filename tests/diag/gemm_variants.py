@@ -1,5 +1,6 @@
-"""Time builds of csrc/pntf_gemm.hip (tests/diag/libgemm_<name>.so, built by hand with other
--DPNTF_GEMM_* values) on the training step's GEMM shapes.  Diagnostics only."""
+"""Time builds of csrc/pntf_gemm.hip (tests/diag/libgemm_<name>.so, built by
+tests/diag/build_gemm.sh with the flags given there, e.g. -DPNTF_CLOCK_STAMP, or of an edited copy
+of the source) on the training step's GEMM shapes.  Diagnostics only."""
 import ctypes
 import os
 import sys

@@ -34,8 +34,7 @@ w[1]·x[1] removed from x6_mma (wgrad_x6_kernel 110-117 at K = 1, panel mode 6 3
 a2b2 pair) and the third split term zeroed in x6_pack_kernel (panel modes 3 / 6 / 7 and
 linear_act schedule 2, 32.1-32.2 on the a1b3 pair).
 
-Not covered: gemm_kernel's 256-column tile (tile_n returns 256 only in a PNTF_GEMM_WIDE=1 build;
-the shipped library never launches it), PNTF_WGRAD_RING (read once at process start), panel modes
+Not covered: PNTF_WGRAD_RING (read once at process start), panel modes
 4 / 5 (compositions of 2 and 3), and pntf_tt_linear_bwd, whose epilogue is always the act adjoint
 (no identity activation; tests/test_tape_kernels.py holds it against the adjoint's reference).
 """
